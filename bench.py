@@ -23,6 +23,13 @@ hash64(namespace/name) mod N (kdtn_topology_shard), one process per GPU:
       empty props, so every record is an UpdateLinks entry (MakeQdiscs-dominated). 1 GPU.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--scaling strong|weak]
+                    [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K epochs, writes the last timed epoch's outputs when
+--dump-outputs is given, and prints the result line. Everything measured beside `value` (the
+per-stage breakdown, rooflines, the re-run with parsed dictionaries, the PCIe-inclusive and
+resident loops, the output stages, CR ingest, the CPU baseline) runs only with --full.
+`--prepare` (run by build()) stores the default workload's tables under .bench_cache/, which
+a run of config 2 at the default size loads instead of generating them.
 One process per GPU. `--gpus N` (N > 1) run without a launcher spawns the N ranks itself:
 the parent starts `torch.distributed.run --nproc-per-node N` as a child process before it
 touches the GPU and exits with the child's status; under an external launcher (WORLD_SIZE
@@ -539,6 +546,56 @@ def dump_outputs(d: str, rank: int, world: int, eng, inp) -> None:
              **{f: getattr(out, f) for f in out.FIELDS})
 
 
+DUMP_BUDGET_BYTES = 48 << 20   # of float64 over all --dump-outputs files of a run (limit: 64 MB)
+
+
+def dump_output_arrays(d: str, rank: int, world: int, eng) -> None:
+    """--dump-outputs: what a caller of the timed path receives for its last epoch
+    (kdtn_epoch_download: every kdtn_batches array, trimmed to the returned counts) as
+    DIR/<name>.npy (<name>_rank<r>.npy beside other ranks), float64: u8 / u32 values as they are,
+    the 16-byte resolve records and 72-byte qdisc records as rows of their u32 words (all exact
+    in float64). A field above its share of the byte budget is written as a fixed sample of its
+    rows, drawn from a generator seeded with the field's position and sorted, so two builds
+    given the same arguments write the same rows. A list the epoch left empty (config 2 deletes
+    and updates nothing) gets no file: its all-zero offsets array already says so."""
+    out = eng.download()
+    os.makedirs(d, exist_ok=True)
+    per_field = DUMP_BUDGET_BYTES // max(world, 1) // len(out.FIELDS) // 8    # float64 values
+    for k, f in enumerate(out.FIELDS):
+        a = getattr(out, f)
+        if len(a) == 0:
+            continue
+        if a.dtype.fields is not None:
+            a = a.view(np.uint32).reshape(len(a), a.dtype.itemsize // 4)
+        rows = max(1, per_field // (a.shape[1] if a.ndim == 2 else 1))
+        if len(a) > rows:
+            a = a[np.sort(np.random.default_rng(k).choice(len(a), rows, replace=False))]
+        name = f if world == 1 else f"{f}_rank{rank}"
+        np.save(os.path.join(d, name + ".npy"), a.astype(np.float64))
+
+
+WORKLOAD_CACHE = os.path.join(ROOT, ".bench_cache")
+
+
+def default_workload(prepare: bool = False):
+    """Config 2 at its default size on one GPU (the headline workload): the generator takes
+    tens of seconds on one host thread, so build() stores its tables once (`--prepare`, through
+    synth.make's cache_dir) and the bench loads them. Stored tables older than the generator
+    library are never used (`--prepare` replaces them); without stored tables, and for every
+    other workload, the generator runs."""
+    names = os.listdir(WORKLOAD_CACHE) if os.path.isdir(WORKLOAD_CACHE) else []
+    stored = [os.path.join(WORKLOAD_CACHE, f) for f in names]
+    stale = [f for f in stored if os.path.getmtime(f) < os.path.getmtime(synth.SYNTH_PATH)]
+    if prepare:
+        for f in stale:
+            os.remove(f)
+        if len(stored) > len(stale):
+            return None                                    # already stored by an earlier build()
+    use = prepare or (stored and not stale)
+    return synth.make(2, total_pods=DEFAULT_PODS[2], shard=0, nshards=1,
+                      cache_dir=WORKLOAD_CACHE if use else None)
+
+
 def free_port() -> int:
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -581,7 +638,19 @@ def main():
     ap.add_argument("--dump", default=None,
                     help="directory: each rank saves its last timed epoch's outputs (rank<r>.npz) for "
                          "an external parity check (tests/test_bench_gpu.py)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="directory: after the timed epochs, write the last one's outputs (what "
+                         "kdtn_epoch_download returns) as DIR/<name>.npy, float64, at most 64 MB in all")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything reported beside `value`: per-stage breakdown, rooflines, "
+                         "parsed-dictionary re-run, PCIe-inclusive and resident loops, output stages, CR "
+                         "ingest, CPU baseline (the --no-* options trim it)")
+    ap.add_argument("--prepare", action="store_true",
+                    help="store the default workload's tables under .bench_cache/ and exit (no GPU)")
     args = ap.parse_args()
+    if args.prepare:
+        default_workload(prepare=True)
+        return
     churn = args.config == 3
     steps = args.steps if args.steps is not None else (10 if churn else 20)
     warmup = args.warmup if args.warmup is not None else (1 if churn else 3)
@@ -616,6 +685,8 @@ def main():
     elif args.config == 1:
         inp = synth.make(1)
         total_pods = inp.topos.n
+    elif args.config == 2 and world == 1 and total_pods == DEFAULT_PODS[2]:
+        inp = default_workload()
     else:
         inp = synth.make(args.config, total_pods=total_pods, shard=rank, nshards=world)
     gen_s = time.time() - t0
@@ -694,20 +765,22 @@ def main():
             assert n == steps, (k, n, steps)                  # every timed epoch was marked
             ksum[k] = ksum.get(k, 0.0) + v
         links_local = inp.desired.n * steps
-        eng.set_timing(2)
-        for _ in range(min(steps, 5)):                    # per-stage breakdown (untimed)
-            run()
-            eng.sync()
-            for k, v in eng.kernel_times().items():
-                bsum[k] = bsum.get(k, 0.0) + v
-            nbreak += 1
-        eng.set_timing(1)
+        if args.full:
+            eng.set_timing(2)
+            for _ in range(min(steps, 5)):                # per-stage breakdown (untimed)
+                run()
+                eng.sync()
+                for k, v in eng.kernel_times().items():
+                    bsum[k] = bsum.get(k, 0.0) + v
+                nbreak += 1
+            eng.set_timing(1)
         counts_acc += np.array([counts.n_add, counts.n_upd, counts.n_del]) * steps
         if args.dump:
             dump_outputs(args.dump, rank, world, eng, inp)
         bytes_acc = reconcile_bytes(inp, counts.n_add, counts.n_upd, counts.n_del) * steps
         epoch_acc = epoch_bytes(inp, counts.n_add, counts.n_upd, counts.n_del) * steps
-        pstats = path_stats(inp)
+        if args.full:
+            pstats = path_stats(inp)
     else:
         # one upload per epoch (untimed), each epoch timed between barriers; sum over epochs
         for ep in range(warmup + steps):
@@ -735,6 +808,8 @@ def main():
             counts_acc += np.array([counts.n_add, counts.n_upd, counts.n_del])
             bytes_acc += reconcile_bytes(inp, counts.n_add, counts.n_upd, counts.n_del)
             epoch_acc += epoch_bytes(inp, counts.n_add, counts.n_upd, counts.n_del)
+            if not args.full:
+                continue
             run(abi.STAGE_DIFF)                      # gate + CalcDiff + lists alone (report)
             eng.sync()
             diff_ms.append(reconcile_ms(eng.kernel_times()))
@@ -747,9 +822,39 @@ def main():
             eng.set_timing(1)
             if pstats is None:
                 pstats = path_stats(inp)
+    if args.dump_outputs:
+        dump_output_arrays(args.dump_outputs, rank, world, eng)
     links_total = allsum(links_local, world)
     nsteps = steps
     ms_step = elapsed / nsteps * 1e3
+    links_per_epoch = links_total / nsteps
+    result = {
+        "metric": "links reconciled/sec (diff+qdisc) on 10M-link topology",
+        "value": links_total / elapsed,
+        "unit": "links/s",
+        "n_gpus": world,
+        "steps": nsteps,
+        "warmup": warmup,
+        "ms_per_step": ms_step,
+        "higher_is_better": True,
+        "scaling": args.scaling,
+        "vs_baseline": None,
+        "dtype": "u32",
+        "data": f"synthetic (kdtn_synth config {args.config}, seed 0x6b64746e), hash-sharded by namespace/name",
+        "config": {"workload": WORKLOAD[args.config].format(pods=total_pods, links=int(links_per_epoch),
+                                                            steps=nsteps),
+                   "config": args.config, "pods_total": total_pods, "links_per_epoch": int(links_per_epoch),
+                   "links_rank0": int(links_local / nsteps), "pods_rank0": inp.topos.n,
+                   "parallelism": f"shard{world} (hash64(ns/name) mod {world})", "exchange": exchange,
+                   "comm_ranks": comm_ranks, "launcher": launcher},
+        "counts_per_epoch_rank0": dict(zip(("add", "upd", "del"), (counts_acc / nsteps).tolist())),
+        "gen_s": round(gen_s, 2),
+    }
+    if not args.full:
+        finish(result, eng, rank, world)
+        return
+    # --full: everything reported beside `value`: the rooflines and per-stage times of the timed
+    # workload, then the stages that take runs of their own
     kavg = {k: v / nsteps for k, v in ksum.items()}           # timed epochs: k_reconcile (+ placement)
     kstage = {k: v / max(nbreak, 1) for k, v in bsum.items()}  # untimed epochs: every stage
     bytes_launch = bytes_acc / nsteps
@@ -771,26 +876,7 @@ def main():
     else:
         roof["traffic_source"] = "no PMC summary of this workload on these kernel sources"
     eb = epoch_acc / nsteps
-    links_per_epoch = links_total / nsteps
-    result = {
-        "metric": "links reconciled/sec (diff+qdisc) on 10M-link topology",
-        "value": links_total / elapsed,
-        "unit": "links/s",
-        "n_gpus": world,
-        "steps": nsteps,
-        "warmup": warmup,
-        "ms_per_step": ms_step,
-        "higher_is_better": True,
-        "scaling": args.scaling,
-        "vs_baseline": None,
-        "dtype": "u32",
-        "data": f"synthetic (kdtn_synth config {args.config}, seed 0x6b64746e), hash-sharded by namespace/name",
-        "config": {"workload": WORKLOAD[args.config].format(pods=total_pods, links=int(links_per_epoch),
-                                                            steps=nsteps),
-                   "config": args.config, "pods_total": total_pods, "links_per_epoch": int(links_per_epoch),
-                   "links_rank0": int(links_local / nsteps), "pods_rank0": inp.topos.n,
-                   "parallelism": f"shard{world} (hash64(ns/name) mod {world})", "exchange": exchange,
-                   "comm_ranks": comm_ranks, "launcher": launcher},
+    result.update({
         "roofline": roof,
         "epoch_roofline": {"bytes": eb, "achieved": eb / (ms_step * 1e-3) / 1e9,
                            "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -798,10 +884,8 @@ def main():
         "kernels_ms": kstage,
         "kernels_ms_note": "per-stage HIP-event times of separate untimed epochs (every stage marked); the timed "
                            "epochs carry events around k_reconcile (+ placement) only (roofline.avg_ms)",
-        "counts_per_epoch_rank0": dict(zip(("add", "upd", "del"), (counts_acc / nsteps).tolist())),
         "k_reconcile_paths_rank0": pstats,
-        "gen_s": round(gen_s, 2),
-    }
+    })
     if not churn:
         # the next epoch over the same CR set: dictionaries resident and already parsed
         # (kdict_keep / pdict_keep = everything); a separate report, not `value`
@@ -882,12 +966,17 @@ def main():
     if world == 1 and not args.no_ingest and args.config == 2:
         progress("CR ingest stage")
         result["ingest_stage"] = ingest_stage(eng, inp, steps)
+    finish(result, eng, rank, world)
+
+
+def finish(result: dict, eng, rank: int, world: int) -> None:
     if rank == 0:
         print(json.dumps(result), flush=True)
     eng.close()
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
 
 
 if __name__ == "__main__":

@@ -34,7 +34,7 @@ def test_bench_gpus2_spawns_two_ranks_with_parity():
     import oracle as O
     from kdtn import synth
     with tempfile.TemporaryDirectory() as d:
-        line = _bench("--gpus", "2", "--pods", str(PODS), "--steps", "3", "--warmup", "1",
+        line = _bench("--gpus", "2", "--pods", str(PODS), "--steps", "3", "--warmup", "1", "--full",
                       "--no-cpu-baseline", "--no-wire", "--no-ingest", "--no-e2e", "--dump", d)
         ranks = [dict(np.load(os.path.join(d, f"rank{r}.npz"))) for r in range(2)]
     assert line["n_gpus"] == 2 and line["config"]["comm_ranks"] == 2
@@ -65,7 +65,7 @@ def synth_tick() -> float:
 
 
 def test_bench_gpus1_line_unchanged():
-    line = _bench("--gpus", "1", "--pods", str(PODS), "--steps", "3", "--warmup", "1",
+    line = _bench("--gpus", "1", "--pods", str(PODS), "--steps", "3", "--warmup", "1", "--full",
                   "--no-cpu-baseline", "--no-wire", "--no-ingest", "--no-e2e")
     assert line["n_gpus"] == 1 and line["config"]["comm_ranks"] == 1
     assert line["config"]["exchange"] == "none" and line["config"]["launcher"] == "none"
@@ -73,6 +73,38 @@ def test_bench_gpus1_line_unchanged():
 
 
 def test_bench_config1_line():
-    line = _bench("--config", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline")
+    line = _bench("--config", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline")
     assert line["n_gpus"] == 1 and line["config"]["config"] == 1
     assert line["counts_per_epoch_rank0"] == {"add": 0.0, "upd": 100000.0, "del": 0.0}
+
+
+FULL_ONLY = ("roofline", "epoch_roofline", "kernels_ms", "k_reconcile_paths_rank0", "epoch_dicts_parsed",
+             "e2e_pcie", "wire_stage", "cpu_baseline", "ingest_stage")
+
+
+def test_bench_plain_run_dumps_the_last_epochs_outputs():
+    """A plain run reports the headline figures alone (everything beside `value` needs --full)
+    and --dump-outputs writes the last timed epoch's outputs as float64 .npy files: at this size
+    no field is sampled, so every file (one per non-empty output) equals the oracle's epoch on
+    the same synthetic input."""
+    import oracle as O
+    from kdtn import synth
+    from kdtn.tables import BatchesOut
+    with tempfile.TemporaryDirectory() as d:
+        line = _bench("--gpus", "1", "--pods", "2000", "--steps", "2", "--warmup", "1", "--dump-outputs", d)
+        got = {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["n_gpus"] == 1
+    assert line["unit"] == "links/s" and line["higher_is_better"] is True and line["dtype"] == "u32"
+    assert line["ms_per_step"] > 0
+    assert abs(line["value"] - line["config"]["links_per_epoch"] / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+    assert not [k for k in FULL_ONLY if k in line], line.keys()
+    inp = synth.make(2, total_pods=2000, shard=0, nshards=1)
+    want = O.reconcile(inp, tick=synth_tick())
+    filled = [f for f in BatchesOut.FIELDS if len(getattr(want, f))]       # an empty list gets no file
+    assert sorted(got) == sorted(filled) and {"action", "add_idx", "add_res", "add_qdisc"} <= set(filled)
+    for f in filled:
+        w = getattr(want, f)
+        if w.dtype.fields is not None:
+            w = w.view(np.uint32).reshape(len(w), w.dtype.itemsize // 4)
+        assert got[f].dtype == np.float64 and got[f].shape == w.shape, (f, got[f].dtype, got[f].shape, w.shape)
+        assert np.array_equal(got[f], w.astype(np.float64)), f

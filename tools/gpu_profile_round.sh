@@ -14,7 +14,7 @@ cd /tmp && export TMPDIR=/tmp
 for C in $CONFIGS; do
   case $C in 2) P=1000000; S=20;; 3) P=1000000; S=5;; 4) P=100000; S=20;; esac
   timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats$C -o run \
-      -- python3 $R/bench.py --config $C --steps $S --no-cpu-baseline --no-ingest --no-wire --no-e2e \
+      -- python3 $R/bench.py --config $C --steps $S --full --no-cpu-baseline --no-ingest --no-wire --no-e2e \
       > $OUT/stats_bench$C.json 2> $OUT/stats$C.err
   echo "config $C stats done"
   timeout -k 10 300 python3 $R/tools/ablate.py --config $C --pods $P --reps 1 --masks DIFF --cache $CACHE \

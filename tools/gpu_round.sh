@@ -45,7 +45,7 @@ fi
 for C in 2 1 3 4; do
   B=bench; [[ $C != 2 ]] && B=bench$C
   if has $B; then
-    timeout -k 10 500 python -u bench.py --config $C ${BENCH_ARGS:-} > $OUT/$B.json 2> $OUT/$B.err
+    timeout -k 10 500 python -u bench.py --full --config $C ${BENCH_ARGS:-} > $OUT/$B.json 2> $OUT/$B.err
     cat $OUT/$B.json
   fi
 done
@@ -69,7 +69,7 @@ for C in 2 3 4; do
   case $C in 2) P=1000000; ST=20;; 3) P=1000000; ST=5;; 4) P=100000; ST=20;; esac
   if has $S; then
     timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$S -o run \
-        -- python3 $R/bench.py --config $C --steps $ST --warmup 3 --no-cpu-baseline > $OUT/${S}_bench.json 2> $OUT/$S.err
+        -- python3 $R/bench.py --config $C --steps $ST --warmup 3 --full --no-cpu-baseline > $OUT/${S}_bench.json 2> $OUT/$S.err
     cat $OUT/${S}_bench.json
   fi
   PM=pmc; [[ $C != 2 ]] && PM=pmc$C
