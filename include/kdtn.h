@@ -740,6 +740,26 @@ int kdtn_vni_download(kdtn_ctx* ctx, kdtn_vni_state* out);
  * 1 k_reconcile and the placement kernels only, 2 every stage (default). */
 int kdtn_set_timing(kdtn_ctx* ctx, int level);
 int kdtn_last_kernel_times(kdtn_ctx* ctx, const char** names, float* ms, int cap);
+/* The launch plan the last kdtn_epoch_run chose from the upload's sizes and the chip (valid
+ * after kdtn_epoch_run + kdtn_epoch_sync). Read-only: a report of values the run computed
+ * anyway, with no setter, so a test can assert which kernels and paths its epoch ran. */
+typedef struct kdtn_plan {
+    uint32_t n_cus;               /* compute units of the device                                */
+    uint32_t nwg;                 /* chunks of 64 Topologies (k_reconcile workgroups / split)   */
+    uint32_t front;               /* 0 serial launches, 1 fused (k_epoch_front + k_pdict_verify),
+                                   * 2 pod lookup tables on a side stream                       */
+    uint32_t diff_build;          /* 1: comparison build of k_reconcile (deferred emission,
+                                   * then k_place_scan + k_place); 0: ticket + look-back build   */
+    uint32_t split;               /* k_reconcile workgroups per chunk                           */
+    uint32_t place;               /* 0 no placement, 1 one wave per chunk, 2 place_parts
+                                   * workgroups per chunk                                       */
+    uint32_t place_parts;         /* workgroups per chunk of the placement (0 when place == 0)  */
+    uint32_t kstrings_parsed;     /* key-dictionary strings this run parsed                     */
+    uint32_t pstrings_parsed;     /* property-dictionary strings this run parsed                */
+    uint32_t first_partial_chunk; /* first chunk holding a Topology not known to emit every
+                                   * record (the full prefix ends there); 0xFFFFFFFF: none      */
+} kdtn_plan;
+int kdtn_epoch_plan(kdtn_ctx* ctx, kdtn_plan* out);
 /* The same marks summed over every epoch synced (kdtn_epoch_sync) since the last reset:
  * names[i], ms[i] (sum over epochs), epochs[i] (epochs that marked it); returns the count.
  * reset != 0 clears the totals after reading (call once with reset = 1 before a timed loop).

@@ -205,6 +205,7 @@ struct kdtn_ctx {
     bool ran = false;
     bool synced = false;   // h_misc[1..4] hold the last run's list totals (kdtn_epoch_sync or counts_fresh)
     uint32_t last_stages = 0;
+    kdtn_plan plan{};      // what the last kdtn_epoch_run chose (kdtn_epoch_plan)
     // multi-GPU
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;
@@ -1262,6 +1263,12 @@ int kdtn_epoch_run(kdtn_ctx* c, uint32_t stages) {
 #endif
     hipStream_t ls = exchange ? c->comm_stream : (side_mode == 2 && c->side_hi ? c->side_hi : c->side_stream);
     const bool side = side_mode && !fused && resolve && pod_rows && !pods_cur && c->T && ls && c->ev_front && c->ev_side;
+    c->plan = kdtn_plan{};
+    c->plan.n_cus = c->n_cus;
+    c->plan.nwg = c->nwg;
+    c->plan.front = fused ? 1u : side ? 2u : 0u;
+    c->plan.kstrings_parsed = c->D - std::min(c->D, c->kd_from & ~63u);
+    c->plan.pstrings_parsed = c->P - std::min(c->P, c->pd_from & ~63u);
     // 4 pod rows per thread in the lookup build (every row load issued before the dependent
     // accesses): rank of 8 0.1761 / 0.1770 → 0.1735 / 0.1744 ms, N = 1 0.7895 → 0.7883 ms
     // (profiles/r05h_pod_per_ab_*)
@@ -1553,6 +1560,8 @@ int kdtn_epoch_run(kdtn_ctx* c, uint32_t stages) {
         }
 #endif
         timer_mark(c, "reconcile", 1);
+        c->plan.diff_build = placed ? 1u : 0u;
+        c->plan.split = w.split;
         if (placed) {
             if ((size_t)c->real.n * 2 > c->del_idx.cap / 4 || (size_t)c->des.n * 2 > c->add_idx.cap / 4) {
                 std::snprintf(g_last_error, sizeof(g_last_error), "deferred placement without upper halves");
@@ -1563,10 +1572,14 @@ int kdtn_epoch_run(kdtn_ctx* c, uint32_t stages) {
             if (c->nwg >= 4u * c->n_cus) {               // enough chunks for a wave each
                 k_place<true><<<(c->nwg + BLOCK / 64 - 1) / (BLOCK / 64), BLOCK, 0, s>>>(
                     T, w.wcount, wbase, w.first_partial_inv, o, w.m_cap, w.n_cap, c->nwg, 1u);
+                c->plan.place = 1;
+                c->plan.place_parts = 1;
             } else {                                      // workgroups per chunk to fill the chip
                 const uint32_t parts = std::min<uint32_t>(16u, std::max<uint32_t>(1u, 4u * c->n_cus / std::max<uint32_t>(c->nwg, 1u)));
                 k_place<false><<<c->nwg * parts, BLOCK, 0, s>>>(T, w.wcount, wbase, w.first_partial_inv, o, w.m_cap,
                                                                 w.n_cap, c->nwg, parts);
+                c->plan.place = 2;
+                c->plan.place_parts = parts;
             }
             timer_mark(c, "place", 1);
         }
@@ -3335,6 +3348,20 @@ int kdtn_vni_download(kdtn_ctx* c, kdtn_vni_state* out) {
 int kdtn_set_timing(kdtn_ctx* c, int level) {
     if (!c || level < 0 || level > 2) return KDTN_EINVAL;
     c->timing = level;
+    return KDTN_OK;
+}
+
+int kdtn_epoch_plan(kdtn_ctx* c, kdtn_plan* out) {
+    if (!c || !out || !c->ran || !c->synced) return KDTN_EINVAL;
+    HIP_TRY(hipSetDevice(c->device));
+    *out = c->plan;
+    out->first_partial_chunk = 0xFFFFFFFFu;
+    if (c->T) {                                      // the sync header's word, stored inverted (0: none)
+        uint32_t* h = c->h_misc + 8;
+        HIP_TRY(hipMemcpyAsync(h, dp<uint32_t>(c->sync) + SYNC_FIRST_PARTIAL_INV, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (*h != 0) out->first_partial_chunk = ~*h;
+    }
     return KDTN_OK;
 }
 

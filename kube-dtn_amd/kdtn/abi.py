@@ -122,6 +122,18 @@ class Counts(C.Structure):
                 ("n_topos", C.c_uint32)]
 
 
+class Plan(C.Structure):
+    """kdtn_plan: the launch plan the last run chose (kdtn_epoch_plan)."""
+    _fields_ = [(f, C.c_uint32) for f in (
+        "n_cus", "nwg", "front", "diff_build", "split", "place", "place_parts", "kstrings_parsed",
+        "pstrings_parsed", "first_partial_chunk")]
+
+
+FRONT_SERIAL, FRONT_FUSED, FRONT_SIDE = 0, 1, 2
+PLACE_NONE, PLACE_WAVE, PLACE_PARTS = 0, 1, 2
+NO_PARTIAL_CHUNK = 0xFFFFFFFF
+
+
 class Wire(C.Structure):
     _fields_ = [("bytes", C.c_void_p), ("cap", C.c_uint64), ("off", C.c_void_p), ("err", C.c_void_p),
                 ("n_bytes", C.c_uint64)]
@@ -202,7 +214,8 @@ EXPORTS = ["kdtn_version", "kdtn_strerror", "kdtn_err_name", "kdtn_init", "kdtn_
            "kdtn_ingest_shard_topos", "kdtn_epoch_remote_encode", "kdtn_epoch_download_remote",
            "kdtn_epoch_commit", "kdtn_epoch_upload_delta", "kdtn_epoch_tables_info",
            "kdtn_vni_ops_export", "kdtn_vni_ops_import", "kdtn_json_ingest_delta",
-           "kdtn_epoch_download_async", "kdtn_epoch_download_wait", "kdtn_epoch_late_pods"]
+           "kdtn_epoch_download_async", "kdtn_epoch_download_wait", "kdtn_epoch_late_pods",
+           "kdtn_epoch_plan"]
 
 
 def ptr(a: np.ndarray, t):

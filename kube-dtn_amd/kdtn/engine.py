@@ -116,6 +116,7 @@ def lib() -> C.CDLL:
         "kdtn_epoch_download_async": (C.c_int, [vp, C.POINTER(abi.Batches)]),
         "kdtn_epoch_download_wait": (C.c_int, [vp]),
         "kdtn_epoch_late_pods": (C.c_int, [vp, vp, C.c_uint32]),
+        "kdtn_epoch_plan": (C.c_int, [vp, C.POINTER(abi.Plan)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -646,6 +647,14 @@ class Engine:
     def set_timing(self, level: int) -> None:
         """HIP-event timing of kdtn_epoch_run: 0 none, 1 k_reconcile (+ placement), 2 every stage."""
         _check(lib().kdtn_set_timing(self._ctx, level), "kdtn_set_timing")
+
+    def plan(self) -> dict[str, int]:
+        """kdtn_epoch_plan: the launch plan of the last run (after run + sync) as a dict of
+        abi.Plan's fields — front (abi.FRONT_*), diff_build, split, place (abi.PLACE_*),
+        place_parts, first_partial_chunk (abi.NO_PARTIAL_CHUNK: none), ..."""
+        p = abi.Plan()
+        _check(lib().kdtn_epoch_plan(self._ctx, C.byref(p)), "kdtn_epoch_plan")
+        return {f: int(getattr(p, f)) for f, _ in abi.Plan._fields_}
 
     def kernel_times(self) -> dict[str, float]:
         names = (C.c_char_p * 32)()

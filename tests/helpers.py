@@ -8,6 +8,7 @@ import numpy as np
 
 from kdtn import abi
 from kdtn.model import Link, LinkProperties, Topology, pack
+from kdtn.tables import BatchesOut, EpochInput, Topos
 
 ACTIONS = {"SKIP": abi.ACT_SKIP, "CREATED": abi.ACT_CREATED, "DIFF": abi.ACT_DIFF}
 
@@ -134,6 +135,27 @@ def random_epoch(seed: int, T: int = 120, big: int = 0, p_err: float = 0.15):
 def random_epoch_input(seed: int, **kw):
     topos, vnis = random_epoch(seed, **kw)
     return topos, pack(topos, vnis)
+
+
+# ---- late pod rows (kdtn_epoch_late_pods): the table the oracle sees -----------------------
+def trim(out: BatchesOut, T: int) -> BatchesOut:
+    """The first T topologies' outputs (the rows after them have no entries)."""
+    assert out.del_off[T] == out.del_off[-1] and out.add_off[T] == out.add_off[-1] and out.upd_off[T] == out.upd_off[-1]
+    return BatchesOut(out.action[:T], out.del_off[:T + 1], out.add_off[:T + 1], out.upd_off[:T + 1],
+                      out.del_idx, out.add_idx, out.upd_idx, out.del_res, out.add_res, out.upd_res,
+                      out.add_qdisc, out.upd_qdisc)
+
+
+def with_rows(inp: EpochInput, kdict, rows: np.ndarray, spec_nil: np.ndarray) -> EpochInput:
+    """inp's table plus one list-less Topology per late row (status = spec: no entries)."""
+    T = inp.topos
+    n = len(rows)
+    nil = np.where(spec_nil, abi.TOPO_SPEC_NIL | abi.TOPO_STATUS_NIL, 0).astype(np.uint8)
+    cat = lambda a, b: np.concatenate([a, b.astype(a.dtype)])
+    topos = Topos(cat(T.ns, rows[:, 0]), cat(T.name, rows[:, 1]), cat(T.src_ip, rows[:, 2]),
+                  cat(T.net_ns, rows[:, 3] & 0x7FFFFFFF), cat(T.flags, nil),
+                  cat(T.real_off, np.full(n, T.real_off[-1])), cat(T.des_off, np.full(n, T.des_off[-1])))
+    return EpochInput(kdict, inp.pdict, topos, inp.realised, inp.desired, inp.vnis)
 
 
 # ---- tricky float strings ----------------------------------------------------------------

@@ -31,6 +31,14 @@ def test_struct_layouts():
     assert C.sizeof(abi.Resolved) == 16
     assert abi.Qdisc.tbf_rate.offset == 56 and abi.Qdisc.err.offset == 70
     assert C.sizeof(abi.Strtab) == 24
+    assert C.sizeof(abi.Plan) == 40 and abi.Plan.first_partial_chunk.offset == 36
+
+
+def test_epoch_plan_is_exported_and_rejects_a_null_context():
+    """kdtn_epoch_plan is among the bound symbols and reports nothing before a run."""
+    assert "kdtn_epoch_plan" in abi.EXPORTS and "kdtn_epoch_plan" in header_functions()
+    p = abi.Plan()
+    assert engine.lib().kdtn_epoch_plan(None, C.byref(p)) == abi.EINVAL
 
 
 def test_host_interner_dedups_and_reserves_empty_id():

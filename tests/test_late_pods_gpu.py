@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 import oracle as O
-from helpers import random_epoch
+from helpers import random_epoch, trim as _trim, with_rows as _with_rows
 from kdtn import abi, synth
 from kdtn.delta import build_delta
 from kdtn.model import Topology, TopologyReconciler, late_pod_rows, pack, peer_misses, unpack
@@ -23,26 +23,6 @@ from kdtn.tables import BatchesOut, EpochInput, Interner, Topos
 
 pytestmark = pytest.mark.gpu
 TICK = 15.625
-
-
-def _trim(out: BatchesOut, T: int) -> BatchesOut:
-    """The first T topologies' outputs (the rows after them have no entries)."""
-    assert out.del_off[T] == out.del_off[-1] and out.add_off[T] == out.add_off[-1] and out.upd_off[T] == out.upd_off[-1]
-    return BatchesOut(out.action[:T], out.del_off[:T + 1], out.add_off[:T + 1], out.upd_off[:T + 1],
-                      out.del_idx, out.add_idx, out.upd_idx, out.del_res, out.add_res, out.upd_res,
-                      out.add_qdisc, out.upd_qdisc)
-
-
-def _with_rows(inp: EpochInput, kdict, rows: np.ndarray, spec_nil: np.ndarray) -> EpochInput:
-    """inp's table plus one list-less Topology per late row (status = spec: no entries)."""
-    T = inp.topos
-    n = len(rows)
-    nil = np.where(spec_nil, abi.TOPO_SPEC_NIL | abi.TOPO_STATUS_NIL, 0).astype(np.uint8)
-    cat = lambda a, b: np.concatenate([a, b.astype(a.dtype)])
-    topos = Topos(cat(T.ns, rows[:, 0]), cat(T.name, rows[:, 1]), cat(T.src_ip, rows[:, 2]),
-                  cat(T.net_ns, rows[:, 3] & 0x7FFFFFFF), cat(T.flags, nil),
-                  cat(T.real_off, np.full(n, T.real_off[-1])), cat(T.des_off, np.full(n, T.des_off[-1])))
-    return EpochInput(kdict, inp.pdict, topos, inp.realised, inp.desired, inp.vnis)
 
 
 def _assert_same(got, want, ctx):
