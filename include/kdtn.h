@@ -524,6 +524,37 @@ typedef struct kdtn_tc_argv {
 int kdtn_epoch_tc(kdtn_ctx* ctx, uint64_t* n_bytes);   /* after run(QDISC|RESOLVE) + sync */
 int kdtn_epoch_download_tc(kdtn_ctx* ctx, kdtn_tc_argv* out);
 
+/* ---- status write-back bodies (status.links JSON) -------------------------------------- */
+/* Reconcile ends with topology.Status.Links = topology.Spec.Links; r.Status().Update(...)
+ * (controllers/topology_controller.go:125-138). For every Topology that reaches that write this
+ * stage produces the bytes of json.Marshal(topology.Status.Links) — the []Link of
+ * api/v1/topology_types.go:59-95 with its LinkProperties (:119-176) — exactly as Go 1.19's
+ * encoding/json writes them (go.mod:3; HTML escaping on, as json.Marshal and the apimachinery
+ * serializer's encoder have it): no whitespace, fields in struct order, the eight Link fields and
+ * `properties` always present, a property omitted when "" (gap: when 0), uid a signed and gap an
+ * unsigned decimal, strings escaped as encodeState.string does (\" \\ \n \r \t; \u00xx for the
+ * other bytes below 0x20 and for < > &; \\u2028 \\u2029; \\ufffd for every byte that starts no
+ * valid UTF-8 sequence). The driver splices the value into the object it sends; metadata,
+ * status.skipped and the rest of the object are not engine state.
+ * Called after kdtn_epoch_run and before kdtn_epoch_commit, like the other output stages. mask
+ * means what it means for kdtn_epoch_commit: NULL = the engine's predicted commit (needs a run
+ * with RESOLVE and QDISC), else mask[t] != 0 = Topology t is committed. The body of Topology t
+ * is bytes[off[t], off[t+1]): the JSON of its spec.links when its action is not KDTN_ACT_SKIP (the
+ * gate returns at :78 and never writes, whatever the mask says) and it is committed, else
+ * empty. A written body is never empty: `null` for a nil spec.links, `[]` for an empty one.
+ * n_written = the written bodies. The stage changes no other state of the context. KDTN_EINVAL
+ * without a run (also after a commit: the context needs a run) and for a Link object of 2 GiB
+ * or more; the download: KDTN_EINVAL before an encode of the last run, KDTN_ENOSPC when
+ * cap < n_bytes. */
+typedef struct kdtn_status_info { uint32_t n_written; uint32_t reserved; uint64_t n_bytes; } kdtn_status_info;
+typedef struct kdtn_status_json {
+    uint8_t*  bytes;  uint64_t cap;     /* in: arena and its capacity            */
+    uint64_t* off;                      /* [T+1]                                 */
+    uint64_t  n_bytes;                  /* out                                   */
+} kdtn_status_json;
+int kdtn_epoch_status_encode(kdtn_ctx* ctx, const uint8_t* mask, kdtn_status_info* info);
+int kdtn_epoch_download_status(kdtn_ctx* ctx, kdtn_status_json* out);
+
 /* ---- CR ingest: TopologyList JSON → device-resident epoch tables ---------------------- */
 /* The step before the diff: the controller's informer lists the
  * Topology CRs as a Kubernetes `TopologyList` JSON document and decodes it with

@@ -181,6 +181,15 @@ struct kdtn_ctx {
     uint64_t tc_bytes = 0;
     uint32_t tc_n = 0;
     bool tc_done = false;
+    // status write-back bodies (kdtn_epoch_status_encode): per-dictionary escape tables with
+    // their watermarks (leading strings whose words are built, like si_k / si_p), selection,
+    // sizes, scans, body offsets, totals block, arena
+    DevBuf kd_esc, pd_esc, sj_mask, sj_sel, sj_tsz, sj_tpos, sj_rsz, sj_rtopo, sj_rpos, sj_off, sj_tot, sj_arena;
+    uint32_t se_k = 0, se_p = 0;
+    bool se_run = false;                       // the escape tables were built since the last run
+    uint64_t sj_bytes = 0;
+    uint32_t sj_T = 0;
+    bool sj_done = false;
     // CR ingest (kdtn_ingest.hip): document, block masks, token stream, decode scratch
     DevBuf j_doc, j_q, j_bs, j_hb, j_esc, j_qcnt, j_qoff, j_tok, j_open, j_close, j_gcnt, j_goff;
     DevBuf j_olist, j_vlist, j_slist;
@@ -718,6 +727,8 @@ int upload_dicts(kdtn_ctx* c, const kdtn_strtab& kd, const kdtn_strtab& pd, uint
     c->pd_from = pk;
     c->si_k = std::min(c->si_k, kk);
     c->si_p = std::min(c->si_p, pk);
+    c->se_k = std::min(c->se_k, kk);
+    c->se_p = std::min(c->se_p, pk);
     TRY(upload_dict(c, c->kd_bytes, c->kd_offs, kd, kk, hs));
     TRY(upload_dict(c, c->pd_bytes, c->pd_offs, pd, pk, hs));
     return prepare_dicts(c);
@@ -922,6 +933,27 @@ StrTab str_tab_pd(kdtn_ctx* c) {
     return StrTab{dp<uint32_t>(c->pd_si), dp<uint8_t>(c->pd_len1), dp<uint8_t>(c->pd_bytes)};
 }
 
+// The JSON escape tables of both dictionaries (k_status_esc), kept like the inline tables: the
+// words of the strings before the upload's keep index stay, the rest are scanned.
+int esc_tables(kdtn_ctx* c) {
+    if (c->se_run && c->se_k == c->D && c->se_p == c->P) return KDTN_OK;
+    hipStream_t s = c->stream;
+    const uint32_t k0 = std::min(c->se_k, c->kd_from), p0 = std::min(c->se_p, c->pd_from);
+    TRY(ensure_keep(c->kd_esc, (size_t)c->D * 4 + 16, (size_t)k0 * 4, s));
+    TRY(ensure_keep(c->pd_esc, (size_t)c->P * 4 + 16, (size_t)p0 * 4, s));
+    if (c->D > k0)
+        k_status_esc<<<nblocks(c->D - k0), BLOCK, 0, s>>>(dp<uint8_t>(c->kd_bytes), dp<uint32_t>(c->kd_offs) + k0,
+                                                         c->D - k0, dp<uint32_t>(c->kd_esc) + k0);
+    if (c->P > p0)
+        k_status_esc<<<nblocks(c->P - p0), BLOCK, 0, s>>>(dp<uint8_t>(c->pd_bytes), dp<uint32_t>(c->pd_offs) + p0,
+                                                         c->P - p0, dp<uint32_t>(c->pd_esc) + p0);
+    HIP_TRY(hipGetLastError());
+    c->se_k = c->D;
+    c->se_p = c->P;
+    c->se_run = true;
+    return KDTN_OK;
+}
+
 // exclusive scan of n u32 values into n+1 u64 offsets (out[n] = total): partial sums, a
 // one-block scan of the partials, the final pass. (A single-pass decoupled look-back over
 // 1024-value blocks measured slower on the output stages: 132 vs 52 us for 10M values, the
@@ -1083,7 +1115,8 @@ void kdtn_destroy(kdtn_ctx* c) {
                       &c->ji_des.buf, &c->ji_real.buf, &c->ji_kmap, &c->ji_pmap, &c->ji_miss, &c->ji_mlen,
                       &c->ji_rank, &c->ji_boff, &c->ji_nil, &c->ji_keep, &c->ji_kpos, &c->ji_claim, &c->ji_res,
                       &c->ji_created, &c->ji_cpos, &c->ji_keys, &c->ji_vals, &c->ji_dkeys, &c->ji_del, &c->ji_ref,
-                      &c->ix_k.slots, &c->ix_p.slots};
+                      &c->ix_k.slots, &c->ix_p.slots, &c->kd_esc, &c->pd_esc, &c->sj_mask, &c->sj_sel, &c->sj_tsz,
+                      &c->sj_tpos, &c->sj_rsz, &c->sj_rtopo, &c->sj_rpos, &c->sj_off, &c->sj_tot, &c->sj_arena};
     for (DevBuf* b : bufs) release(*b);
     retired_flush();
     for (int i = 0; i <= kMaxTimers; ++i)
@@ -1599,6 +1632,8 @@ int kdtn_epoch_run(kdtn_ctx* c, uint32_t stages) {
     c->fan_valid = false;
     c->lc_valid = false;
     c->si_run = false;
+    c->se_run = false;
+    c->sj_done = false;
     c->rp_done = false;
     c->vx_imported = false;
     c->vx_contest_ok = false;
@@ -1946,7 +1981,7 @@ int kdtn_make_qdiscs(kdtn_ctx* c, const kdtn_strtab* pdict, const kdtn_props_tab
     const uint32_t P = pdict->n, n = props->n;
     for (int k = 0; k < KDTN_NPROP; ++k) TRY(check_ids(props->prop[k], n, P, "props"));
     if (n && !props->gap) return KDTN_EINVAL;
-    c->pd_valid = c->pd_from = c->si_p = 0;                // this call owns the property tables now
+    c->pd_valid = c->pd_from = c->si_p = c->se_p = 0;                // this call owns the property tables now
     c->ix_p.n = c->ix_p.mask = 0;
     c->uploaded = false;
     TRY(upload_arena(c, c->pd_bytes, pdict->bytes, pdict->offs[P]));
@@ -2351,6 +2386,99 @@ int kdtn_epoch_download_tc(kdtn_ctx* c, kdtn_tc_argv* o) {
     return KDTN_OK;
 }
 
+int kdtn_epoch_status_encode(kdtn_ctx* c, const uint8_t* mask, kdtn_status_info* info) {
+    if (!c || !c->ran) return KDTN_EINVAL;
+    if (!mask && !fanout_stages_ok(c)) {
+        std::snprintf(g_last_error, sizeof(g_last_error),
+                      "kdtn_epoch_status_encode without a mask needs a run with the resolve and qdisc stages");
+        return KDTN_EINVAL;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    TRY(counts_fresh(c));
+    hipStream_t s = c->stream;
+    const uint32_t T = c->T, N = c->des.n;
+    TRY(ensure(c->sj_sel, (size_t)T + 16));
+    TRY(ensure(c->sj_tsz, (size_t)T * 4 + 16));
+    TRY(ensure(c->sj_tpos, ((size_t)T + 1) * 8));
+    TRY(ensure(c->sj_rsz, (size_t)N * 4 + 16));
+    TRY(ensure(c->sj_rtopo, (size_t)N * 4 + 16));
+    TRY(ensure(c->sj_rpos, ((size_t)N + 1) * 8));
+    TRY(ensure(c->sj_off, ((size_t)T + 1) * 8));
+    TRY(ensure(c->sj_tot, ST_TOT_WORDS * 4));
+    c->n_ev = 0;
+    (void)hipEventRecord(c->ev[0], s);
+    TRY(str_tables(c));
+    TRY(esc_tables(c));
+    timer_mark(c, "status_tables");
+    const uint8_t* dmask = nullptr;
+    const uint32_t* cut = nullptr;
+    if (mask) {
+        TRY(upload(c, c->sj_mask, mask, T));
+        dmask = dp<uint8_t>(c->sj_mask);
+    } else {
+        TRY(run_reach(c, nullptr, 0));                      // per-topology first failing entries
+        cut = dp<uint32_t>(c->f_cut);
+    }
+    uint32_t* tot = dp<uint32_t>(c->sj_tot);
+    HIP_TRY(hipMemsetAsync(tot, 0, ST_TOT_WORDS * 4, s));
+    StatusIn in{c->des.view, topo_view(c), str_tab_kd(c), str_tab_pd(c), dp<uint32_t>(c->kd_offs),
+                dp<uint32_t>(c->pd_offs), dp<uint32_t>(c->kd_esc), dp<uint32_t>(c->pd_esc), dp<uint8_t>(c->sj_sel),
+                dp<uint32_t>(c->sj_rsz), dp<uint32_t>(c->sj_rtopo), dp<uint64_t>(c->sj_rpos),
+                dp<uint32_t>(c->sj_tsz), dp<uint64_t>(c->sj_tpos)};
+    if (T)
+        k_status_select<<<nblocks(T), BLOCK, 0, s>>>(in.T, dp<uint8_t>(c->action), cut, dmask, dp<uint8_t>(c->sj_sel),
+                                                     dp<uint32_t>(c->sj_tsz), tot);
+    if (N) k_status_sizes<<<nblocks(N), BLOCK, 0, s>>>(in, dp<uint32_t>(c->sj_rsz), dp<uint32_t>(c->sj_rtopo), tot);
+    timer_mark(c, "status_sizes");
+    TRY(scan_u32(c, dp<uint32_t>(c->sj_rsz), N, dp<uint64_t>(c->sj_rpos)));
+    TRY(scan_u32(c, dp<uint32_t>(c->sj_tsz), T, dp<uint64_t>(c->sj_tpos)));
+    k_status_offsets<<<nblocks((uint64_t)T + 1), BLOCK, 0, s>>>(in, dp<uint64_t>(c->sj_off), tot);
+    timer_mark(c, "status_scan");
+    HIP_TRY(hipGetLastError());
+    uint32_t h[ST_TOT_WORDS] = {};
+    HIP_TRY(hipMemcpyAsync(h, tot, sizeof h, hipMemcpyDeviceToHost, s));   // the one read: n_written, n_bytes
+    HIP_TRY(hipStreamSynchronize(s));
+    if (h[ST_TOT_ERR]) {
+        std::snprintf(g_last_error, sizeof(g_last_error), "a Link object of 2 GiB or more");
+        return KDTN_EINVAL;
+    }
+    uint64_t total;
+    std::memcpy(&total, h + ST_TOT_BYTES, 8);
+    uint32_t nw = 0;
+    for (int k = 0; k < 32; ++k) nw += h[k];
+    TRY(ensure(c->sj_arena, (size_t)total + 64));
+    timer_mark(c, "status_host_sync");
+    const uint32_t nwb = nblocks(N), ntb = nblocks(T);
+    if (nwb + ntb)
+        k_status_write<<<nwb + ntb, BLOCK, 0, s>>>(in, dp<uint64_t>(c->sj_off), nwb, dp<uint8_t>(c->sj_arena));
+    if (h[ST_TOT_BIG]) k_status_write_big<<<nwb, BLOCK, 0, s>>>(in, dp<uint8_t>(c->sj_arena));
+    timer_mark(c, "status_write");
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    c->sj_bytes = total;
+    c->sj_T = T;
+    c->sj_done = true;
+    if (info) {
+        info->n_written = nw;
+        info->reserved = 0;
+        info->n_bytes = total;
+    }
+    return KDTN_OK;
+}
+
+int kdtn_epoch_download_status(kdtn_ctx* c, kdtn_status_json* o) {
+    if (!c || !o || !c->ran || !c->sj_done) return KDTN_EINVAL;
+    HIP_TRY(hipSetDevice(c->device));
+    o->n_bytes = c->sj_bytes;
+    if (o->bytes && c->sj_bytes > o->cap) return KDTN_ENOSPC;
+    hipStream_t s = c->stream;
+    if (o->bytes && c->sj_bytes) HIP_TRY(hipMemcpyAsync(o->bytes, c->sj_arena.p, c->sj_bytes, hipMemcpyDeviceToHost, s));
+    if (o->off) HIP_TRY(hipMemcpyAsync(o->off, c->sj_off.p, ((size_t)c->sj_T + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return KDTN_OK;
+}
+
 }  // extern "C"
 
 // ======================================================================================
@@ -2733,7 +2861,7 @@ static int json_ingest_full(kdtn_ctx* c, const kdtn_vni_table* vnis, kdtn_ingest
     c->uploaded = false;
     c->ran = false;
     c->kd_valid = c->pd_valid = c->kd_from = c->pd_from = 0;   // the document's dictionaries are new
-    c->si_k = c->si_p = 0;
+    c->si_k = c->si_p = c->se_k = c->se_p = 0;
     c->ix_k.n = c->ix_k.mask = c->ix_p.n = c->ix_p.mask = 0;     // (their string indexes too)
     const JsTargets tg{&c->t_ns, &c->t_name, &c->t_src, &c->t_netns, &c->t_flags, &c->t_roff, &c->t_noff,
                        &c->des, &c->real, &c->kd_bytes, &c->kd_offs, &c->pd_bytes, &c->pd_offs};
@@ -3505,6 +3633,8 @@ void state_changed(kdtn_ctx* c) {
     c->fan_valid = false;
     c->lc_valid = false;
     c->si_run = false;
+    c->se_run = false;
+    c->sj_done = false;
     c->rp_done = false;
     c->j_done = false;
     c->tables_cur = false;
@@ -3828,7 +3958,7 @@ int kdtn_epoch_upload_delta(kdtn_ctx* c, const kdtn_epoch_delta* d) {
         c->kd_arena = saved_arena[0], c->pd_arena = saved_arena[1];
         c->uploaded = !(err & DERR_KEEP);
         if (err & DERR_KEEP) {                     // the resident strings themselves are suspect
-            c->kd_valid = c->pd_valid = c->si_k = c->si_p = 0;
+            c->kd_valid = c->pd_valid = c->si_k = c->si_p = c->se_k = c->se_p = 0;
             c->ix_k.n = c->ix_k.mask = 0;
             c->ix_p.n = c->ix_p.mask = 0;
         }
@@ -4194,6 +4324,8 @@ int kdtn_json_ingest_delta(kdtn_ctx* c, const uint32_t* deleted, uint32_t n_dele
     c->pd_valid = c->pd_from = P0;
     c->si_k = std::min(c->si_k, D0);
     c->si_p = std::min(c->si_p, P0);
+    c->se_k = std::min(c->se_k, D0);
+    c->se_p = std::min(c->se_p, P0);
     TRY(prepare_dicts(c));
     TRY(check_vnis(c, vn, D1, D0));
     TRY(prepare_vnis(c, vn));

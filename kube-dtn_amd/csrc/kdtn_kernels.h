@@ -379,6 +379,42 @@ struct TcIn {
 __global__ void k_tc_sizes(TcIn w, uint32_t* size);
 __global__ void k_tc_write(TcIn w, const uint64_t* off, uint8_t* arena);
 
+// ---- status write-back bodies: json.Marshal(status.links) (kdtn_status.hip) ----------------
+constexpr int STATUS_WIN = 16384;       // LDS bytes per wave of k_status_write: 64 objects of ~125 B of key
+                                        // text + ~100 B of strings fit one round (64 KB per block: 2 blocks
+                                        // = 8 waves per CU of the 160 KB LDS)
+// Escape table of a dictionary (k_status_esc), one word per string: the length of the string as
+// encoding/json writes it between the quotes, SE_REWRITE when that differs from its bytes (the
+// writer then runs the byte automaton instead of copying). SE_LEN = SE_OVERFLOW: 2 GiB or more.
+constexpr int STATUS_WAVES = 2;         // waves per SIMD the 64-KB blocks leave room for: the writer's register budget
+constexpr uint32_t SE_REWRITE = 0x80000000u, SE_LEN = 0x7FFFFFFFu, SE_OVERFLOW = 0x7FFFFFFFu;
+// totals block of a status encode (u32 words): 32 counters of written bodies (summed by the
+// host), the arena size (u64), an error word (an object of 4 GiB or more), whether an object may
+// exceed the writer's window
+enum : int { ST_TOT_BYTES = 32, ST_TOT_ERR = 34, ST_TOT_BIG = 35, ST_TOT_WORDS = 36 };
+struct StatusIn {
+    DevLinks N;                     // the desired store (spec.links)
+    DevTopos T;
+    StrTab kd, pd;                  // inline string tables (plain strings: one gather)
+    const uint32_t* kd_offs;        // dictionary offsets (strings that are rewritten)
+    const uint32_t* pd_offs;
+    const uint32_t* kesc;           // escape tables
+    const uint32_t* pesc;
+    const uint8_t* sel;             // [T] the Topology's body is written
+    const uint32_t* rsz;            // [N] bytes of each record's object with its [ , ] (0: not written)
+    const uint32_t* rtopo;          // [N] Topology of each record
+    const uint64_t* rpos;           // [N+1] exclusive scan of rsz
+    const uint32_t* tsz;            // [T] bytes a written Topology without records carries (null, [])
+    const uint64_t* tpos;           // [T+1] exclusive scan of tsz
+};
+__global__ void k_status_esc(const uint8_t* bytes, const uint32_t* offs, uint32_t n, uint32_t* esc);
+__global__ void k_status_select(DevTopos T, const uint8_t* action, const uint32_t* cut, const uint8_t* mask,
+                                uint8_t* sel, uint32_t* tsz, uint32_t* tot);
+__global__ void k_status_sizes(StatusIn s, uint32_t* rsz, uint32_t* rtopo, uint32_t* tot);
+__global__ void k_status_offsets(StatusIn s, uint64_t* off, uint32_t* tot);
+__global__ void k_status_write(StatusIn s, const uint64_t* off, uint32_t nwb, uint8_t* arena);
+__global__ void k_status_write_big(StatusIn s, uint8_t* arena);
+
 // ---- resident epoch state: status commit and delta upload (kdtn_state.hip) -----------------
 enum : uint8_t { ASM_SEG_A = 0, ASM_SEG_B = 1, ASM_REF = 2 };   // source of a topology's new segment
 __global__ void k_commit_plan(DevTopos T, const uint8_t* action, const uint32_t* cut, const uint8_t* mask,

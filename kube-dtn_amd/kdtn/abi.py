@@ -148,6 +148,15 @@ class TcArgv(C.Structure):
     _fields_ = [("bytes", C.c_void_p), ("cap", C.c_uint64), ("off", C.c_void_p), ("n_bytes", C.c_uint64)]
 
 
+class StatusInfo(C.Structure):
+    """kdtn_status_info: written bodies and arena bytes of a kdtn_epoch_status_encode."""
+    _fields_ = [("n_written", C.c_uint32), ("reserved", C.c_uint32), ("n_bytes", C.c_uint64)]
+
+
+class StatusJson(C.Structure):
+    _fields_ = [("bytes", C.c_void_p), ("cap", C.c_uint64), ("off", C.c_void_p), ("n_bytes", C.c_uint64)]
+
+
 class RemoteInfo(C.Structure):
     _fields_ = [("n_msgs", C.c_uint32), ("n_remote", C.c_uint32), ("n_bytes", C.c_uint64),
                 ("n_tc_bytes", C.c_uint64)]
@@ -215,7 +224,7 @@ EXPORTS = ["kdtn_version", "kdtn_strerror", "kdtn_err_name", "kdtn_init", "kdtn_
            "kdtn_epoch_commit", "kdtn_epoch_upload_delta", "kdtn_epoch_tables_info",
            "kdtn_vni_ops_export", "kdtn_vni_ops_import", "kdtn_json_ingest_delta",
            "kdtn_epoch_download_async", "kdtn_epoch_download_wait", "kdtn_epoch_late_pods",
-           "kdtn_epoch_plan"]
+           "kdtn_epoch_plan", "kdtn_epoch_status_encode", "kdtn_epoch_download_status"]
 
 
 def ptr(a: np.ndarray, t):

@@ -117,6 +117,8 @@ def lib() -> C.CDLL:
         "kdtn_epoch_download_wait": (C.c_int, [vp]),
         "kdtn_epoch_late_pods": (C.c_int, [vp, vp, C.c_uint32]),
         "kdtn_epoch_plan": (C.c_int, [vp, C.POINTER(abi.Plan)]),
+        "kdtn_epoch_status_encode": (C.c_int, [vp, vp, C.POINTER(abi.StatusInfo)]),
+        "kdtn_epoch_download_status": (C.c_int, [vp, C.POINTER(abi.StatusJson)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -563,6 +565,29 @@ class Engine:
         t = abi.TcArgv(arena.ctypes.data, arena.size, off.ctypes.data, 0)
         _check(lib().kdtn_epoch_download_tc(self._ctx, C.byref(t)), "kdtn_epoch_download_tc")
         return arena[:int(n.value)], off
+
+    # ---- status write-back bodies (status.links JSON) -----------------------------------
+    def status_encode(self, mask=None):
+        """kdtn_epoch_status_encode: json.Marshal(status.links) of every Topology whose
+        Reconcile writes its status, on the GPU (after run, before commit). mask as for
+        commit(): None = the engine's predicted commit. Returns (n_written, n_bytes)."""
+        info = abi.StatusInfo()
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+        _check(lib().kdtn_epoch_status_encode(self._ctx, m.ctypes.data if m is not None else None, C.byref(info)),
+               "kdtn_epoch_status_encode")
+        return int(info.n_written), int(info.n_bytes)
+
+    def status_json(self):
+        """(arena uint8, off uint64[T+1]) of the last status_encode: the body of Topology t is
+        arena[off[t]:off[t+1]], empty when it is not written."""
+        o = abi.StatusJson()
+        _check(lib().kdtn_epoch_download_status(self._ctx, C.byref(o)), "kdtn_epoch_download_status")
+        n = int(o.n_bytes)
+        arena = np.zeros(max(n, 1), np.uint8)
+        off = np.zeros(self._T + 1, np.uint64)
+        o.bytes, o.cap, o.off = arena.ctypes.data, arena.size, off.ctypes.data
+        _check(lib().kdtn_epoch_download_status(self._ctx, C.byref(o)), "kdtn_epoch_download_status")
+        return arena[:n], off
 
     def fanout(self):
         """RemotePod RPCs of the last epoch grouped per destination daemon:
