@@ -454,7 +454,10 @@ int kdtn_epoch_download_wire(kdtn_ctx* ctx, kdtn_wire* out);
  * reference sends one RPC per link;
  * here they are grouped per destination daemon (peer status.src_ip = kdtn_resolved.vtep):
  * node[k] = kdict id of daemon k (ascending), its entries idx[off[k] .. off[k+1]) are
- * add-list entry indices in add-list order. Requires a run with RESOLVE and QDISC. */
+ * add-list entry indices in add-list order. Requires a run with RESOLVE and QDISC.
+ * An epoch whose RemotePods go to more than 8192 destination daemons (FAN_NODE_CAP) is
+ * KDTN_EINVAL here and in kdtn_epoch_remote_encode (kdtn_strerror names the count); the run's
+ * other stages (download, encode, tc) and the context's later epochs stay usable. */
 typedef struct kdtn_fanout {
     uint32_t* node;          /* [node_cap]                                            */
     uint32_t* off;           /* [node_cap + 1]                                        */

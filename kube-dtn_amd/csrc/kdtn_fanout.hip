@@ -119,7 +119,7 @@ __global__ void __launch_bounds__(BLOCK) k_fan_nodes_write(const uint32_t* mark,
         for (uint32_t w = m[k]; w; w &= w - 1u) {
             const uint32_t id = (b0 + k) * 4u + ((uint32_t)__builtin_ctz(w) >> 3);
             node_idx[id] = (uint32_t)x;
-            nodes[x] = id;
+            if (x < (uint64_t)FAN_NODE_CAP) nodes[x] = id;  // over the cap: counted, refused by the host
             ++x;
         }
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *n_nodes = (uint32_t)(part[blockIdx.x] + tot);
