@@ -22,6 +22,8 @@
  *   kdtn_diff             replaces CalcDiff + the Reconcile gate alone
  *   kdtn_resolve          replaces the pure prefix of the daemon's AddLinks / DelLinks for
  *                         one LinksBatchQuery (handler.go:592-632)
+ *   kdtn_wire_ingest      replaces proto.Unmarshal of the LinksBatchQuery request bodies in front
+ *                         of those handlers (proto/v1/kube_dtn.proto:8-53), for a stream of them
  *   kdtn_epoch_encode     replaces Link.ToProto + proto.Marshal of the batches
  *   kdtn_epoch_fanout     groups the daemons' UpdateRemote RPCs (common/utils.go:39-67)
  *                         per destination daemon
@@ -643,6 +645,70 @@ int kdtn_json_ingest_delta(kdtn_ctx* ctx, const uint32_t* deleted, uint32_t n_de
  * or an ingest — into info (n_topos, n_desired, n_realised, dictionary sizes); after it,
  * kdtn_ingest_download returns those tables (the resident state after a commit). */
 int kdtn_epoch_tables_info(kdtn_ctx* ctx, kdtn_ingest_info* info);
+
+/* ---- daemon-side ingest: LinksBatchQuery streams → device-resident epoch tables --------- */
+/* The inverse of kdtn_epoch_encode: the request bodies of Local.AddLinks / DelLinks / UpdateLinks
+ * as they arrive on the wire, decoded on the GPU. Replaces proto.Unmarshal into
+ * pb.LinksBatchQuery in front of the batch handlers (daemon/kubedtn/handler.go:592-671; message
+ * definitions proto/v1/kube_dtn.proto:8-53) and the host interning and SoA build a caller of
+ * kdtn_resolve / kdtn_epoch_upload would do. The stream goes up with kdtn_json_upload (a plain
+ * byte copy; 4 GiB or more is KDTN_EINVAL); message m = stream[off[m], off[m+1]) (off ascending,
+ * off[n_msgs] <= the uploaded size, else KDTN_EINVAL) becomes Topology m of the result:
+ *   - LocalPod.KubeNs / Name / SrcIp / NetNs → ns / name / src_ip / net_ns (an absent LocalPod:
+ *     four empty strings, Go's nil message read through its getters);
+ *   - kind KDTN_BATCH_ADD / KDTN_BATCH_UPD: the links are the Topology's desired segment, its
+ *     realised list empty and non-nil; KDTN_BATCH_DEL: the links are its realised segment, the
+ *     desired list empty and non-nil. With the gate and CalcDiff an ADD message comes out of
+ *     kdtn_epoch_run as one add batch and a DEL message as one del batch, planned as the
+ *     daemon's handler would. Planning UPD messages (UpdateLinks: MakeQdiscs per link) is not
+ *     done by the epoch run: it stays with kdtn_make_qdiscs over the decoded tables;
+ *   - a rejected message (err[m] != 0) is a Topology with both lists and its four strings empty;
+ *     decoding goes on with the next message (per-message errors are data, not return codes).
+ * Dictionaries as kdtn_json_ingest leaves them: id 0 = "", no duplicates, ids ranked by the
+ * lowest stream offset of a surviving value of the string (a value a later occurrence of its
+ * field overrides, or one in a rejected message, does not count).
+ * Decoding follows protobuf-go's proto.Unmarshal for proto3: fields in any order; unknown field
+ * numbers, and known ones carrying another wire type, skipped by wire type; a repeated scalar or
+ * string keeps its last value; repeated local_pod / properties sub-messages merge field by field;
+ * links append; uid = the 64-bit varint as two's complement, gap = the low 32 bits of its varint;
+ * every string landing in a known string field must be valid UTF-8 (overridden ones included).
+ * Documented deviation: groups (wire types 3, 4) are refused as KDTN_WIRE_GROUP where Go skips
+ * a well-formed unknown group (decode such a message on the host). When a message has several
+ * faults, err[m] is the one at the lowest offset among those the passes meet.
+ * info as for kdtn_json_ingest (json_err 0; n_tokens = the fields walked). Afterwards
+ * kdtn_epoch_tables_info, kdtn_ingest_download and kdtn_epoch_run work as after kdtn_json_ingest.
+ * Single-shard contexts only. A string of 16 MiB or more is KDTN_EINVAL. */
+#define KDTN_BATCH_UPD 2   /* UpdateLinks (handler.go:634-671), beside KDTN_BATCH_ADD / _DEL */
+typedef enum kdtn_wire_err {
+    KDTN_WIRE_OK = 0,
+    KDTN_WIRE_TRUNCATED,   /* a length past its enclosing message, or a cut-off field          */
+    KDTN_WIRE_VARINT,      /* a varint longer than 10 bytes, or whose 10th byte is above 1     */
+    KDTN_WIRE_TAG,         /* field number 0 (or above 2^29 - 1), wire type 6 or 7             */
+    KDTN_WIRE_UTF8,        /* a known string field that is not valid UTF-8                     */
+    KDTN_WIRE_GROUP        /* wire type 3 or 4 (host fallback)                                 */
+} kdtn_wire_err;
+typedef struct kdtn_wire_in {
+    uint32_t        n_msgs;
+    const uint64_t* off;     /* [n_msgs+1] message m = stream[off[m], off[m+1])                */
+    const uint8_t*  kind;    /* [n_msgs]   KDTN_BATCH_ADD / DEL / UPD                          */
+    uint8_t*        err;     /* [n_msgs]   out: kdtn_wire_err per message (may be NULL)        */
+} kdtn_wire_in;
+int kdtn_wire_ingest(kdtn_ctx* ctx, const kdtn_wire_in* in, kdtn_ingest_info* info);
+/* What the last kdtn_wire_ingest did (read-only report, like kdtn_epoch_plan): the frame pass
+ * walks a message from a window of window_bytes of on-chip memory, one lane per message; a
+ * message that does not fit one window ((off[m] & 15) + its size > window_bytes) takes a whole
+ * wave, whose window slides over it. */
+typedef struct kdtn_wire_plan {
+    uint32_t window_bytes;
+    uint32_t n_long;          /* messages that went the long way                              */
+    uint32_t first_long;      /* the first of them, 0xFFFFFFFF: none                          */
+    uint32_t n_link_frames;   /* links elements found (rejected messages' included)           */
+    uint32_t n_pod_frames;    /* local_pod occurrences found                                  */
+    uint32_t n_rejected;      /* messages with err != 0                                       */
+    uint32_t intern_passes;   /* 1 + the times an intern table was grown and the pass rerun   */
+    uint32_t reserved;
+} kdtn_wire_plan;
+int kdtn_wire_ingest_plan(kdtn_ctx* ctx, kdtn_wire_plan* out);
 
 /* Sharded ingest for one rank of nshards (SURVEY §8(e) with §8(f) rank 2). Every controller
  * replica's informer holds the whole Topology store (the controller watches all Topologies,

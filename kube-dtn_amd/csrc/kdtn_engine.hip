@@ -202,6 +202,11 @@ struct kdtn_ctx {
     uint64_t j_n = 0;
     uint32_t j_nb = 0;
     bool j_loaded = false, j_done = false;
+    // LinksBatchQuery decode (kdtn_wire_ingest): message table, frame lists, per-message state
+    DevBuf u_off, u_kind, u_nl, u_np, u_loff, u_poff, u_lfr, u_lmsg, u_pfr, u_merr, u_ctl;
+    DevBuf u_cdes, u_creal, u_des64, u_real64, u_rbase, u_err8;
+    kdtn_wire_plan u_plan{};
+    bool u_done = false;
     kdtn_ingest_info j_info{};
     // host-visible counters
     hipEvent_t ev_done = nullptr;  // the epoch's last command (kdtn_epoch_sync polls it)
@@ -1116,7 +1121,10 @@ void kdtn_destroy(kdtn_ctx* c) {
                       &c->ji_rank, &c->ji_boff, &c->ji_nil, &c->ji_keep, &c->ji_kpos, &c->ji_claim, &c->ji_res,
                       &c->ji_created, &c->ji_cpos, &c->ji_keys, &c->ji_vals, &c->ji_dkeys, &c->ji_del, &c->ji_ref,
                       &c->ix_k.slots, &c->ix_p.slots, &c->kd_esc, &c->pd_esc, &c->sj_mask, &c->sj_sel, &c->sj_tsz,
-                      &c->sj_tpos, &c->sj_rsz, &c->sj_rtopo, &c->sj_rpos, &c->sj_off, &c->sj_tot, &c->sj_arena};
+                      &c->sj_tpos, &c->sj_rsz, &c->sj_rtopo, &c->sj_rpos, &c->sj_off, &c->sj_tot, &c->sj_arena,
+                      &c->u_off, &c->u_kind, &c->u_nl, &c->u_np, &c->u_loff, &c->u_poff, &c->u_lfr, &c->u_lmsg,
+                      &c->u_pfr, &c->u_merr, &c->u_ctl, &c->u_cdes, &c->u_creal, &c->u_des64, &c->u_real64,
+                      &c->u_rbase, &c->u_err8};
     for (DevBuf* b : bufs) release(*b);
     retired_flush();
     for (int i = 0; i <= kMaxTimers; ++i)
@@ -2852,21 +2860,35 @@ static int json_decode(kdtn_ctx* c, const JsTargets& tg, JsCounts* o, kdtn_inges
     return KDTN_OK;
 }
 
-static int json_ingest_full(kdtn_ctx* c, const kdtn_vni_table* vnis, kdtn_ingest_info* info) {
-    if (!c || !c->j_loaded) return KDTN_EINVAL;
-    HIP_TRY(hipSetDevice(c->device));
+// A full ingest (JSON or wire) replaces the context's tables: what it resets first, where it
+// decodes to, and (ingest_install) what kdtn_epoch_upload would set up around the decoded tables.
+static void ingest_reset(kdtn_ctx* c) {
     c->sh_T = 0;
     g_last_error[0] = 0;
-    hipStream_t s = c->stream;
     c->uploaded = false;
     c->ran = false;
     c->kd_valid = c->pd_valid = c->kd_from = c->pd_from = 0;   // the document's dictionaries are new
     c->si_k = c->si_p = c->se_k = c->se_p = 0;
     c->ix_k.n = c->ix_k.mask = c->ix_p.n = c->ix_p.mask = 0;     // (their string indexes too)
-    const JsTargets tg{&c->t_ns, &c->t_name, &c->t_src, &c->t_netns, &c->t_flags, &c->t_roff, &c->t_noff,
-                       &c->des, &c->real, &c->kd_bytes, &c->kd_offs, &c->pd_bytes, &c->pd_offs};
+}
+static JsTargets ingest_targets(kdtn_ctx* c) {
+    return JsTargets{&c->t_ns, &c->t_name, &c->t_src, &c->t_netns, &c->t_flags, &c->t_roff, &c->t_noff,
+                     &c->des, &c->real, &c->kd_bytes, &c->kd_offs, &c->pd_bytes, &c->pd_offs};
+}
+static int ingest_install(kdtn_ctx* c, const JsCounts& k, const kdtn_vni_table* vnis, kdtn_ingest_info* info);
+
+static int json_ingest_full(kdtn_ctx* c, const kdtn_vni_table* vnis, kdtn_ingest_info* info) {
+    if (!c || !c->j_loaded) return KDTN_EINVAL;
+    HIP_TRY(hipSetDevice(c->device));
+    ingest_reset(c);
+    const JsTargets tg = ingest_targets(c);
     JsCounts k{};
     TRY(json_decode(c, tg, &k, info));
+    return ingest_install(c, k, vnis, info);
+}
+
+static int ingest_install(kdtn_ctx* c, const JsCounts& k, const kdtn_vni_table* vnis, kdtn_ingest_info* info) {
+    hipStream_t s = c->stream;
     const uint32_t T = k.T, N = k.N, M = k.M;
     const uint64_t kbytes = k.kbytes, pbytes = k.pbytes;
     c->T = T;
@@ -2905,6 +2927,201 @@ int kdtn_json_ingest(kdtn_ctx* c, const kdtn_vni_table* vnis, kdtn_ingest_info* 
         return KDTN_EINVAL;
     }
     return json_ingest_full(c, vnis, info);
+}
+
+// LinksBatchQuery streams → the context's epoch tables (kdtn_unwire.hip). Host round trips:
+// the frame totals (to size the frame lists), the record totals with the error bytes (to size
+// the stores), the intern status (again only when a table is grown), then the dictionary finish's.
+int kdtn_wire_ingest(kdtn_ctx* c, const kdtn_wire_in* in, kdtn_ingest_info* info) {
+    if (!c || !in || !c->j_loaded || (in->n_msgs && (!in->off || !in->kind))) return KDTN_EINVAL;
+    end_shard_ingest(c);
+    if (c->nranks > 1) {
+        std::snprintf(g_last_error, sizeof(g_last_error), "kdtn_wire_ingest: single-shard contexts");
+        return KDTN_EINVAL;
+    }
+    const uint32_t T = in->n_msgs;
+    for (uint32_t m = 0; m < T; ++m) {
+        if (in->off[m + 1] < in->off[m] || in->off[m + 1] > c->j_n || in->kind[m] > KDTN_BATCH_UPD) {
+            std::snprintf(g_last_error, sizeof(g_last_error),
+                          "kdtn_wire_ingest: message %u: offsets must ascend within the uploaded %llu bytes, kind <= 2",
+                          m, (unsigned long long)c->j_n);
+            return KDTN_EINVAL;
+        }
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    ingest_reset(c);
+    hipStream_t s = c->stream;
+    c->u_done = false;
+    c->j_done = false;
+    c->j_info = kdtn_ingest_info{};
+    c->n_ev = 0;
+    (void)hipEventRecord(c->ev[0], s);
+    const JsTargets tg = ingest_targets(c);
+
+    // 1. the message table, the top-level count pass and its scans
+    TRY(ensure(c->u_off, ((size_t)T + 1) * 8));
+    TRY(ensure(c->u_kind, (size_t)T));
+    for (DevBuf* b : {&c->u_nl, &c->u_np, &c->u_cdes, &c->u_creal, &c->u_rbase}) TRY(ensure(*b, (size_t)T * 4));
+    for (DevBuf* b : {&c->u_loff, &c->u_poff, &c->u_des64, &c->u_real64, &c->u_merr}) TRY(ensure(*b, ((size_t)T + 1) * 8));
+    TRY(ensure(c->u_err8, (size_t)T));
+    TRY(ensure(c->u_ctl, UW_CTL_WORDS * 8));
+    TRY(ensure(c->j_small, J_SMALL));
+    if (T) {
+        HIP_TRY(hipMemcpyAsync(c->u_off.p, in->off, ((size_t)T + 1) * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(c->u_kind.p, in->kind, T, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(hipMemsetAsync(c->u_merr.p, 0xFF, ((size_t)T + 1) * 8, s));
+    HIP_TRY(hipMemsetAsync(c->u_ctl.p, 0, UW_CTL_WORDS * 8, s));
+    HIP_TRY(hipMemsetAsync(dp<unsigned long long>(c->u_ctl) + UW_CTL_FIRST_LONG, 0xFF, 8, s));
+    const UwIn ui{dp<uint8_t>(c->j_doc), (uint32_t)c->j_n, (uint32_t)((size_t)c->j_nb * 64 + 128), T,
+                  dp<uint64_t>(c->u_off), dp<uint8_t>(c->u_kind)};
+    UwFrames fr{dp<uint32_t>(c->u_nl), dp<uint32_t>(c->u_np), dp<uint64_t>(c->u_loff), dp<uint64_t>(c->u_poff),
+                nullptr, nullptr, nullptr, dp<unsigned long long>(c->u_merr), dp<unsigned long long>(c->u_ctl)};
+    const uint32_t nwave = nblocks(T, 64);
+    if (T) k_uw_frame<false><<<nwave, UW_BLOCK, 0, s>>>(ui, fr);
+    TRY(scan_u32(c, fr.nl, T, dp<uint64_t>(c->u_loff)));
+    TRY(scan_u32(c, fr.np, T, dp<uint64_t>(c->u_poff)));
+    timer_mark(c, "uw_frame_count");
+    uint64_t nlf64 = 0, npf64 = 0;
+    TRY(d2h(c, &nlf64, fr.loff + T));
+    TRY(d2h(c, &npf64, fr.poff + T));
+    HIP_TRY(hipStreamSynchronize(s));
+    timer_mark(c, "uw_sync");
+    HIP_TRY(hipGetLastError());
+    if (nlf64 >= 0xFFFFFFFFull || npf64 >= 0xFFFFFFFFull) {
+        std::snprintf(g_last_error, sizeof(g_last_error), "kdtn_wire_ingest: too many links for one stream");
+        return KDTN_EINVAL;
+    }
+    const uint32_t NF = (uint32_t)nlf64, NP = (uint32_t)npf64;
+
+    // 2. frames, then the nested decode for its errors; record counts per side
+    TRY(ensure(c->u_lfr, (size_t)NF * 8));
+    TRY(ensure(c->u_lmsg, (size_t)NF * 4));
+    TRY(ensure(c->u_pfr, (size_t)NP * 8));
+    fr.lfr = dp<uint2>(c->u_lfr);
+    fr.lmsg = dp<uint32_t>(c->u_lmsg);
+    fr.pfr = dp<uint2>(c->u_pfr);
+    for (DevBuf* b : {tg.ns, tg.name, tg.src, tg.netns, &c->j_tflags}) TRY(ensure(*b, (size_t)T * 4));
+    TRY(ensure(*tg.flags, (size_t)T));
+    TRY(ensure(*tg.roff, ((size_t)T + 1) * 4));
+    TRY(ensure(*tg.noff, ((size_t)T + 1) * 4));
+    JsTopoOut to{dp<uint32_t>(*tg.ns), dp<uint32_t>(*tg.name), dp<uint32_t>(*tg.src), dp<uint32_t>(*tg.netns),
+                 dp<uint32_t>(c->j_tflags), dp<uint32_t>(*tg.roff), dp<uint32_t>(*tg.noff)};
+    JsIntern it{};
+    const JsStore none{nullptr};
+    if (T) k_uw_frame<true><<<nwave, UW_BLOCK, 0, s>>>(ui, fr);
+    timer_mark(c, "uw_frame_write");
+    if (NF) k_uw_links<false><<<nblocks(NF, 64), UW_BLOCK, 0, s>>>(ui, fr, NF, nullptr, none, none, it);
+    if (T) k_uw_pods<false><<<nblocks(T), BLOCK, 0, s>>>(ui, fr, to, it);
+    timer_mark(c, "uw_check");
+    if (T) k_uw_counts<<<nblocks(T), BLOCK, 0, s>>>(ui, fr, dp<uint32_t>(c->u_cdes), dp<uint32_t>(c->u_creal),
+                                                   dp<uint8_t>(c->u_err8));
+    TRY(scan_u32(c, dp<uint32_t>(c->u_cdes), T, dp<uint64_t>(c->u_des64)));
+    TRY(scan_u32(c, dp<uint32_t>(c->u_creal), T, dp<uint64_t>(c->u_real64)));
+    k_uw_offsets<<<nblocks((uint64_t)T + 1), BLOCK, 0, s>>>(ui, dp<uint64_t>(c->u_des64), dp<uint64_t>(c->u_real64), to,
+                                                            dp<uint32_t>(c->u_rbase));
+    timer_mark(c, "uw_counts");
+    uint64_t n64 = 0, m64 = 0;
+    unsigned long long ctl[UW_CTL_WORDS] = {};
+    TRY(d2h(c, &n64, dp<uint64_t>(c->u_des64) + T));
+    TRY(d2h(c, &m64, dp<uint64_t>(c->u_real64) + T));
+    TRY(d2h(c, ctl, c->u_ctl.p, UW_CTL_WORDS));
+    std::vector<uint8_t> herr(T);
+    if (T) HIP_TRY(hipMemcpyAsync(herr.data(), c->u_err8.p, T, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    timer_mark(c, "uw_sync");
+    HIP_TRY(hipGetLastError());
+    const uint32_t N = (uint32_t)n64, M = (uint32_t)m64;
+    uint32_t nrej = 0;
+    for (uint32_t m = 0; m < T; ++m) nrej += herr[m] != 0;
+    if (in->err && T) std::memcpy(in->err, herr.data(), T);
+    c->j_info.n_tokens = ctl[UW_CTL_FIELDS];
+
+    // 3. stores, intern tables; the intern pass, rerun with larger tables when one fills up
+    TRY(link_store_alloc(c, *tg.des, N));
+    TRY(link_store_alloc(c, *tg.real, M));
+    const uint64_t des_tiles = ((uint64_t)N + TILE_RECS - 1) / TILE_RECS, real_tiles = ((uint64_t)M + TILE_RECS - 1) / TILE_RECS;
+    const size_t rows_bytes = (size_t)(des_tiles + real_tiles) * TILE_WORDS * 4;
+    TRY(ensure(c->j_rows, std::max<size_t>(rows_bytes, 16)));
+    const JsStore des{dp<uint32_t>(c->j_rows)};
+    const JsStore real{dp<uint32_t>(c->j_rows) + (size_t)des_tiles * TILE_WORDS};
+    uint32_t kcap = std::max(c->j_kcap, next_pow2(std::max<uint64_t>(1024, 2ull * ((uint64_t)N + M) + 4ull * T)));
+    uint32_t pcap = std::max(c->j_pcap, next_pow2(std::max<uint64_t>(1024, ((uint64_t)N + M) / 2 + 64)));
+    unsigned long long* small = dp<unsigned long long>(c->j_small);
+    TRY(ensure(c->j_heap, 64));                          // (no decoded strings: wire strings are raw bytes)
+    uint32_t passes = 0;
+    for (int attempt = 0;; ++attempt) {
+        TRY(ensure(c->j_kslots, (size_t)kcap * sizeof(JsSlot)));
+        TRY(ensure(c->j_krep, (size_t)kcap * 4));
+        TRY(ensure(c->j_pslots, (size_t)pcap * sizeof(JsSlot)));
+        TRY(ensure(c->j_prep, (size_t)pcap * 4));
+        TRY(ensure(c->j_kkeys, (size_t)kcap * 8));
+        TRY(ensure(c->j_pkeys, (size_t)pcap * 8));
+        HIP_TRY(hipMemsetAsync(c->j_kslots.p, 0, (size_t)kcap * sizeof(JsSlot), s));
+        HIP_TRY(hipMemsetAsync(c->j_kkeys.p, 0, (size_t)kcap * 8, s));
+        HIP_TRY(hipMemsetAsync(c->j_pkeys.p, 0, (size_t)pcap * 8, s));
+        HIP_TRY(hipMemsetAsync(c->j_krep.p, 0xFF, (size_t)kcap * 4, s));
+        HIP_TRY(hipMemsetAsync(c->j_pslots.p, 0, (size_t)pcap * sizeof(JsSlot), s));
+        HIP_TRY(hipMemsetAsync(c->j_prep.p, 0xFF, (size_t)pcap * 4, s));
+        HIP_TRY(hipMemsetAsync(small, 0, J_SMALL, s));
+        for (DevBuf* b : {tg.ns, tg.name, tg.src, tg.netns, &c->j_tflags})   // rejected messages: "" and no flags
+            if (T) HIP_TRY(hipMemsetAsync(b->p, 0, (size_t)T * 4, s));
+        if (rows_bytes) HIP_TRY(hipMemsetAsync(c->j_rows.p, 0, rows_bytes, s));
+        it = JsIntern{};
+        it.doc = ui.doc;
+        it.heap = dp<uint8_t>(c->j_heap);
+        it.heap_used = small + 2;
+        it.status = reinterpret_cast<uint32_t*>(small + 3);
+        it.kd = JsDict{dp<JsSlot>(c->j_kslots), dp<unsigned long long>(c->j_kkeys), dp<uint32_t>(c->j_krep), kcap - 1};
+        it.pd = JsDict{dp<JsSlot>(c->j_pslots), dp<unsigned long long>(c->j_pkeys), dp<uint32_t>(c->j_prep), pcap - 1};
+        if (NF) k_uw_links<true><<<nblocks(NF, 64), UW_BLOCK, 0, s>>>(ui, fr, NF, dp<uint32_t>(c->u_rbase), des, real, it);
+        if (T) k_uw_pods<true><<<nblocks(T), BLOCK, 0, s>>>(ui, fr, to, it);
+        timer_mark(c, "uw_intern");
+        unsigned long long st = 0;
+        TRY(d2h(c, &st, small + 3));
+        HIP_TRY(hipStreamSynchronize(s));
+        timer_mark(c, "uw_sync");
+        HIP_TRY(hipGetLastError());
+        ++passes;
+        if ((uint32_t)st & JS_ST_LONG) {
+            std::snprintf(g_last_error, sizeof(g_last_error), "kdtn_wire_ingest: a string is longer than 16 MiB");
+            return KDTN_EINVAL;
+        }
+        if ((uint32_t)st & JS_ST_OVERFLOW) {
+            if (attempt >= 6) return KDTN_ENOMEM;
+            kcap = (uint32_t)std::min<uint64_t>((uint64_t)kcap * 4, 1u << 31);
+            pcap = (uint32_t)std::min<uint64_t>((uint64_t)pcap * 4, 1u << 31);
+            continue;
+        }
+        break;
+    }
+
+    // 4. the ingest's finish: first-occurrence ids (occurrence = stream offset / 2), dictionaries
+    uint64_t kbytes = 0, pbytes = 0;
+    uint32_t D = 0, P = 0;
+    const uint32_t nocc = (uint32_t)(c->j_n / 2 + 1);
+    TRY(json_dict(c, it.kd, it, nocc, c->j_kslot_id, *tg.kd_bytes, *tg.kd_offs, &D, &kbytes));
+    TRY(json_dict(c, it.pd, it, nocc, c->j_pslot_id, *tg.pd_bytes, *tg.pd_offs, &P, &pbytes));
+    c->j_kcap = std::max(kcap, next_pow2(2ull * D));
+    c->j_pcap = std::max(pcap, next_pow2(2ull * P));
+    if (N) k_js_finalize_links<<<(uint32_t)des_tiles, BLOCK, 0, s>>>(des.base, dp<uint32_t>(tg.des->buf),
+                                                                       dp<uint32_t>(c->j_kslot_id), dp<uint32_t>(c->j_pslot_id));
+    if (M) k_js_finalize_links<<<(uint32_t)real_tiles, BLOCK, 0, s>>>(real.base, dp<uint32_t>(tg.real->buf),
+                                                                        dp<uint32_t>(c->j_kslot_id), dp<uint32_t>(c->j_pslot_id));
+    if (T) k_js_finalize_topos<<<nblocks(T), BLOCK, 0, s>>>(to, T, dp<uint32_t>(c->j_kslot_id), dp<uint8_t>(*tg.flags));
+    timer_mark(c, "js_intern");
+    HIP_TRY(hipGetLastError());
+    c->u_plan = kdtn_wire_plan{UW_WIN, (uint32_t)ctl[UW_CTL_N_LONG], (uint32_t)ctl[UW_CTL_FIRST_LONG], NF, NP, nrej, passes, 0u};
+    const JsCounts k{T, N, M, D, P, kbytes, pbytes};
+    TRY(ingest_install(c, k, nullptr, info));
+    c->u_done = true;
+    return KDTN_OK;
+}
+
+int kdtn_wire_ingest_plan(kdtn_ctx* c, kdtn_wire_plan* out) {
+    if (!c || !out || !c->u_done) return KDTN_EINVAL;
+    *out = c->u_plan;
+    return KDTN_OK;
 }
 
 // The whole document decoded as for one GPU, then the epoch cut down to this shard's

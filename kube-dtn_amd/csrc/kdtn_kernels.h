@@ -838,6 +838,38 @@ __global__ void k_js_finalize_links(const uint32_t* rows, uint32_t* tiles, const
                                     const uint32_t* pslot_id);
 __global__ void k_js_finalize_topos(JsTopoOut to, uint32_t T, const uint32_t* kslot_id, uint8_t* flags8);
 
+// ---- LinksBatchQuery decode: protobuf streams → epoch tables (kdtn_unwire.hip) -------------
+constexpr uint32_t UW_WIN = 16384;           // a wave's LDS window over the stream, bytes
+constexpr int UW_BLOCK = 64;                 // one wave per workgroup in the windowed passes
+enum : int { UW_CTL_FIELDS = 0, UW_CTL_FIRST_LONG = 1, UW_CTL_N_LONG = 2, UW_CTL_WORDS = 3 };
+struct UwIn {
+    const uint8_t* doc;        // the stream, padded past its end (kdtn_json_upload)
+    uint32_t n, lim;           // stream bytes; readable bytes (a multiple of 16)
+    uint32_t n_msgs;
+    const uint64_t* off;       // [n_msgs + 1]
+    const uint8_t* kind;       // [n_msgs] KDTN_BATCH_*
+};
+struct UwFrames {
+    uint32_t* nl;              // [n_msgs] links elements of the message (0 when its top level fails)
+    uint32_t* np;              // [n_msgs] local_pod occurrences
+    const uint64_t* loff;      // [n_msgs + 1] scans of nl, np
+    const uint64_t* poff;
+    uint2* lfr;                // link frames: (offset, length)
+    uint32_t* lmsg;            // message of each link frame
+    uint2* pfr;                // local_pod frames
+    unsigned long long* merr;  // [n_msgs] first error: offset << 8 | kdtn_wire_err, ~0 = none
+    unsigned long long* ctl;   // UW_CTL_*: fields walked, first long message, long messages
+};
+template <bool WRITE>
+__global__ void k_uw_frame(UwIn in, UwFrames f);
+template <bool INTERN>
+__global__ void k_uw_links(UwIn in, UwFrames f, uint32_t nfr, const uint32_t* rbase, JsStore des, JsStore real,
+                           JsIntern it);
+template <bool INTERN>
+__global__ void k_uw_pods(UwIn in, UwFrames f, JsTopoOut to, JsIntern it);
+__global__ void k_uw_counts(UwIn in, UwFrames f, uint32_t* cdes, uint32_t* creal, uint8_t* err8);
+__global__ void k_uw_offsets(UwIn in, const uint64_t* des64, const uint64_t* real64, JsTopoOut to, uint32_t* rbase);
+
 // sharded ingest (kdtn_json_ingest_shard): keep[t] = this shard owns topology t; then the
 // kept topologies' columns and records compacted into fresh tables (document order kept)
 __global__ void k_shard_mark(DevTopos T, const uint8_t* kd_bytes, const uint32_t* kd_offs, uint32_t nshards,

@@ -28,32 +28,6 @@
 namespace kdtn {
 
 
-// ---- dictionary UTF-8 validity (Go unicode/utf8.ValidString) ---------------------------
-KD_INLINE bool utf8_ok(const uint8_t* s, uint32_t n) {
-    uint32_t i = 0;
-    while (i < n) {
-        const uint32_t c = s[i];
-        if (c < 0x80u) { ++i; continue; }
-        uint32_t need, lo = 0x80u, hi = 0xBFu;
-        if (c >= 0xC2u && c <= 0xDFu) need = 1;
-        else if (c == 0xE0u) { need = 2; lo = 0xA0u; }
-        else if (c >= 0xE1u && c <= 0xECu) need = 2;
-        else if (c == 0xEDu) { need = 2; hi = 0x9Fu; }
-        else if (c >= 0xEEu && c <= 0xEFu) need = 2;
-        else if (c == 0xF0u) { need = 3; lo = 0x90u; }
-        else if (c >= 0xF1u && c <= 0xF3u) need = 3;
-        else if (c == 0xF4u) { need = 3; hi = 0x8Fu; }
-        else return false;
-        if (i + need >= n) return false;
-        const uint32_t c1 = s[i + 1];
-        if (c1 < lo || c1 > hi) return false;
-        for (uint32_t k = 2; k <= need; ++k)
-            if (s[i + k] < 0x80u || s[i + k] > 0xBFu) return false;
-        i += need + 1;
-    }
-    return true;
-}
-
 // One thread per dictionary string: its inline entry (W dwords; StrTab) and its length byte.
 // The string's first 32 bytes come from one 16-B load pair (+ a dword); only strings with a
 // byte >= 0x80 run the UTF-8 automaton. Bytes of an inline entry past the string are zero.

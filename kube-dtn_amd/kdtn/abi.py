@@ -172,7 +172,17 @@ class PodTable(C.Structure):
                 ("flags", u8p)]
 
 
-BATCH_ADD, BATCH_DEL = 0, 1
+BATCH_ADD, BATCH_DEL, BATCH_UPD = 0, 1, 2
+WIRE_OK, WIRE_TRUNCATED, WIRE_VARINT, WIRE_TAG, WIRE_UTF8, WIRE_GROUP = range(6)   # kdtn_wire_err
+
+
+class WireIn(C.Structure):
+    _fields_ = [("n_msgs", C.c_uint32), ("off", C.c_void_p), ("kind", C.c_void_p), ("err", C.c_void_p)]
+
+
+class WirePlan(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("window_bytes", "n_long", "first_long", "n_link_frames",
+                                          "n_pod_frames", "n_rejected", "intern_passes", "reserved")]
 
 
 class IngestInfo(C.Structure):
@@ -224,7 +234,8 @@ EXPORTS = ["kdtn_version", "kdtn_strerror", "kdtn_err_name", "kdtn_init", "kdtn_
            "kdtn_epoch_commit", "kdtn_epoch_upload_delta", "kdtn_epoch_tables_info",
            "kdtn_vni_ops_export", "kdtn_vni_ops_import", "kdtn_json_ingest_delta",
            "kdtn_epoch_download_async", "kdtn_epoch_download_wait", "kdtn_epoch_late_pods",
-           "kdtn_epoch_plan", "kdtn_epoch_status_encode", "kdtn_epoch_download_status"]
+           "kdtn_epoch_plan", "kdtn_epoch_status_encode", "kdtn_epoch_download_status",
+           "kdtn_wire_ingest", "kdtn_wire_ingest_plan"]
 
 
 def ptr(a: np.ndarray, t):

@@ -119,6 +119,8 @@ def lib() -> C.CDLL:
         "kdtn_epoch_plan": (C.c_int, [vp, C.POINTER(abi.Plan)]),
         "kdtn_epoch_status_encode": (C.c_int, [vp, vp, C.POINTER(abi.StatusInfo)]),
         "kdtn_epoch_download_status": (C.c_int, [vp, C.POINTER(abi.StatusJson)]),
+        "kdtn_wire_ingest": (C.c_int, [vp, C.POINTER(abi.WireIn), C.POINTER(abi.IngestInfo)]),
+        "kdtn_wire_ingest_plan": (C.c_int, [vp, C.POINTER(abi.WirePlan)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -386,6 +388,31 @@ class Engine:
     def ingest(self, doc: bytes, vnis=None, shard=None) -> abi.IngestInfo:
         self.json_upload(doc)
         return self.json_ingest(vnis, shard)
+
+    def wire_ingest(self, stream: bytes, off, kind):
+        """kdtn_wire_ingest: a stream of LinksBatchQuery messages (message m = stream[off[m],
+        off[m+1]), kind[m] = abi.BATCH_ADD / DEL / UPD) decoded on the GPU into the epoch tables,
+        one Topology per message. Returns (IngestInfo, err): err[m] = kdtn_wire_err of message m."""
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        kind = np.ascontiguousarray(kind, dtype=np.uint8)
+        if len(off) != len(kind) + 1:
+            raise ValueError("off must hold one more entry than kind")
+        self.json_upload(bytes(stream))
+        err = np.zeros(len(kind), np.uint8)
+        win = abi.WireIn(len(kind), off.ctypes.data, kind.ctypes.data if len(kind) else None,
+                         err.ctypes.data if len(kind) else None)
+        info = abi.IngestInfo()
+        _check(lib().kdtn_wire_ingest(self._ctx, C.byref(win), C.byref(info)), "kdtn_wire_ingest")
+        self._T = info.n_topos
+        self._caps = (info.n_realised, info.n_desired, info.n_realised)
+        self._ingest = info
+        return info, err
+
+    def wire_plan(self) -> abi.WirePlan:
+        """What the last wire_ingest did (kdtn_wire_ingest_plan)."""
+        p = abi.WirePlan()
+        _check(lib().kdtn_wire_ingest_plan(self._ctx, C.byref(p)), "kdtn_wire_ingest_plan")
+        return p
 
     def ingest_doc_index(self) -> np.ndarray:
         """Document index of each topology of the last ingest (kdtn_ingest_shard_topos)."""
