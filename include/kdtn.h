@@ -30,6 +30,9 @@
  *   kdtn_epoch_tc         synthesises SetVethQdiscs' `tc ... tbf` argv (common/qdisc.go:252-266)
  *   kdtn_epoch_remote_encode  marshals the RemotePod bodies of Remote.Update
  *                         (common/utils.go:39-67, daemon/kubedtn/handler.go:348-371)
+ *   kdtn_remote_ingest    replaces, on the daemon that receives those bodies, proto.Unmarshal into
+ *                         pb.RemotePod and the pure prefix of KubeDTN.Update
+ *                         (daemon/kubedtn/handler.go:149-198) for a batch of them
  *   kdtn_epoch_late_pods  getPod's API-server fallback on an informer miss
  *                         (daemon/kubedtn/handler.go:35-39): late pod rows for the lookup
  *
@@ -709,6 +712,73 @@ typedef struct kdtn_wire_plan {
     uint32_t reserved;
 } kdtn_wire_plan;
 int kdtn_wire_ingest_plan(kdtn_ctx* ctx, kdtn_wire_plan* out);
+
+/* ---- daemon-side ingest: RemotePod bodies → Remote.Update plans ------------------------- */
+/* The receiving side of kdtn_epoch_remote_encode: the request bodies of Remote.Update as a gRPC
+ * server hands them over, decoded and planned on the GPU, one fixed-size plan per message.
+ * Replaces, once per message, proto.Unmarshal into pb.RemotePod (proto/v1/kube_dtn.proto:65-79)
+ * and the pure prefix of KubeDTN.Update (daemon/kubedtn/handler.go:149-198): the VNI conflict
+ * check (:177-185), SetupVxLan's MakeQdiscs(pod.Properties) (daemon/vxlan/vxlan.go:40,
+ * common/qdisc.go:20-126) and CreateOrUpdate's net.ParseCIDR(IntfIp) (vxlan.go:80-83).
+ * The receive buffer goes up with kdtn_json_upload (a plain byte copy). Bodies are bare RemotePod
+ * messages (not the delimited stream kdtn_epoch_download_remote returns: strip each length
+ * varint), body m = stream[start[m], start[m] + size[m]). They need not touch nor ascend (a
+ * receive buffer has gRPC's 5-byte frame headers between them); a body reaching past the
+ * uploaded size is KDTN_EINVAL. n_msgs == 0 and n_vni == 0 are valid.
+ * Decoding is kdtn_wire_ingest's, for this message: fields in any order; unknown field numbers,
+ * and known ones carrying another wire type, skipped by wire type; a repeated string or vni
+ * keeps its last value; repeated properties occurrences merge field by field; every value
+ * landing in a known string field (the 12 property strings too) must be valid UTF-8, overridden
+ * ones included; vni and gap are the low 32 bits of their varints; groups are refused
+ * (KDTN_WIRE_GROUP, the same documented deviation). wire_err is the first fault in stream order
+ * (one sequential walk per message); a rejected message does not disturb its neighbours; a
+ * zero-length body is a valid message of defaults.
+ * Plan: err = KDTN_E_REMOTE_CIDR when IntfIp != "" and net.ParseCIDR fails, else the first
+ * failing MakeQdiscs step (KDTN_E_LATENCY … KDTN_E_RATE), else 0. qdisc[m] =
+ * MakeQdiscs(properties) whatever the CIDR says: what kdtn_make_qdiscs returns for the same
+ * twelve strings and gap (absent properties: the empty record, like nil).
+ * The snapshot is the daemon's VxlanManager map at batch start (daemon/vxlan/manager.go:14-17):
+ * entry i holds vni[i] for the netns string vni_ns[i]; a vni listed twice resolves to its lowest
+ * entry. vni_conflict compares the netns BYTES. Every message is answered against the snapshot:
+ * the order of vxlanManager.Add (:192) among concurrent calls has no reference answer (one
+ * handler goroutine per call), so the map after the batch stays with the host that runs the
+ * syscalls, as do RemoveLinkWithVni and SetupVxLan's netlink part.
+ * The call leaves the context's epoch state (tables, outputs, resident map) as it was. */
+enum { KDTN_RP_NET_NS, KDTN_RP_INTF_NAME, KDTN_RP_INTF_IP, KDTN_RP_PEER_VTEP,
+       KDTN_RP_KUBE_NS, KDTN_RP_NAME, KDTN_RP_NSTR };            /* RemotePod fields 1-5, 8 */
+typedef struct kdtn_remote_str { uint32_t off, len; } kdtn_remote_str;   /* value bytes in the stream; len 0 => off 0 */
+typedef struct kdtn_remote_plan {          /* 64 bytes per message */
+    kdtn_remote_str str[KDTN_RP_NSTR];     /* the surviving (last) value of each string field */
+    int32_t  vni;                          /* field 6: low 32 bits of the varint */
+    uint32_t vni_entry;                    /* snapshot entry holding vni, 0xFFFFFFFF: none */
+    uint8_t  wire_err;                     /* kdtn_wire_err; != 0: every other field is 0 */
+    uint8_t  err;                          /* kdtn_err of SetupVxLan's pure prefix, above */
+    uint8_t  vni_conflict;                 /* handler.go:177-185: entry found and its netns != NetNs */
+    uint8_t  has_props;                    /* a properties field was present */
+    uint32_t reserved;
+} kdtn_remote_plan;
+typedef struct kdtn_remote_in {
+    uint32_t        n_msgs;
+    const uint64_t* start;   /* [n_msgs] body m = stream[start[m], start[m] + size[m]) */
+    const uint32_t* size;    /* [n_msgs] */
+    uint32_t        n_vni;   /* the daemon's VxlanManager map at batch start */
+    const int32_t*  vni;     /* [n_vni] */
+    kdtn_strtab     vni_ns;  /* n_vni strings: the netns each vni is stored with (no id-0 rule here) */
+} kdtn_remote_in;
+int kdtn_remote_ingest(kdtn_ctx* ctx, const kdtn_remote_in* in, kdtn_remote_plan* plan /*[n_msgs]*/,
+                       kdtn_qdisc* qdisc /*[n_msgs], may be NULL*/);
+/* What the last kdtn_remote_ingest did (read-only report): each wave of 64 consecutive messages
+ * walks them from a window of window_bytes of on-chip memory. n_direct counts the messages read
+ * straight from memory instead: a body that does not fit one window ((start[m] & 15) + size[m] >
+ * window_bytes), and every body of a wave whose starts do not ascend or leave more than
+ * window_bytes between the end of one body and the start of the next. */
+typedef struct kdtn_remote_ingest_plan_t {
+    uint32_t window_bytes;
+    uint32_t n_direct;
+    uint32_t n_rejected;      /* messages with wire_err != 0 */
+    uint32_t n_conflict;      /* messages with vni_conflict set */
+} kdtn_remote_ingest_plan_t;
+int kdtn_remote_ingest_plan(kdtn_ctx* ctx, kdtn_remote_ingest_plan_t* out);
 
 /* Sharded ingest for one rank of nshards (SURVEY §8(e) with §8(f) rank 2). Every controller
  * replica's informer holds the whole Topology store (the controller watches all Topologies,

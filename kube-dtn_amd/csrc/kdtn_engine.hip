@@ -207,6 +207,10 @@ struct kdtn_ctx {
     DevBuf u_cdes, u_creal, u_des64, u_real64, u_rbase, u_err8;
     kdtn_wire_plan u_plan{};
     bool u_done = false;
+    // RemotePod planning (kdtn_remote_ingest): body table, VNI snapshot and table, outputs, report
+    DevBuf ri_start, ri_size, ri_vni, ri_nsb, ri_nso, ri_slots, ri_plan, ri_qd, ri_ctl;
+    kdtn_remote_ingest_plan_t ri_report{};
+    bool ri_done = false;
     kdtn_ingest_info j_info{};
     // host-visible counters
     hipEvent_t ev_done = nullptr;  // the epoch's last command (kdtn_epoch_sync polls it)
@@ -1124,7 +1128,8 @@ void kdtn_destroy(kdtn_ctx* c) {
                       &c->sj_tpos, &c->sj_rsz, &c->sj_rtopo, &c->sj_rpos, &c->sj_off, &c->sj_tot, &c->sj_arena,
                       &c->u_off, &c->u_kind, &c->u_nl, &c->u_np, &c->u_loff, &c->u_poff, &c->u_lfr, &c->u_lmsg,
                       &c->u_pfr, &c->u_merr, &c->u_ctl, &c->u_cdes, &c->u_creal, &c->u_des64, &c->u_real64,
-                      &c->u_rbase, &c->u_err8};
+                      &c->u_rbase, &c->u_err8, &c->ri_start, &c->ri_size, &c->ri_vni, &c->ri_nsb, &c->ri_nso,
+                      &c->ri_slots, &c->ri_plan, &c->ri_qd, &c->ri_ctl};
     for (DevBuf* b : bufs) release(*b);
     retired_flush();
     for (int i = 0; i <= kMaxTimers; ++i)
@@ -3121,6 +3126,74 @@ int kdtn_wire_ingest(kdtn_ctx* c, const kdtn_wire_in* in, kdtn_ingest_info* info
 int kdtn_wire_ingest_plan(kdtn_ctx* c, kdtn_wire_plan* out) {
     if (!c || !out || !c->u_done) return KDTN_EINVAL;
     *out = c->u_plan;
+    return KDTN_OK;
+}
+
+// RemotePod bodies → Remote.Update plans (kdtn_remote.hip). Two launches and one
+// synchronisation: the report block and the records come back together. Touches only its own
+// buffers and the uploaded bytes, so the context's epoch state stays as it was.
+int kdtn_remote_ingest(kdtn_ctx* c, const kdtn_remote_in* in, kdtn_remote_plan* plan, kdtn_qdisc* qdisc) {
+    if (!c || !in || !c->j_loaded) return KDTN_EINVAL;
+    const uint32_t n = in->n_msgs, nv = in->n_vni;
+    if ((n && (!in->start || !in->size || !plan)) || (nv && (!in->vni || !in->vni_ns.offs || in->vni_ns.n != nv)))
+        return KDTN_EINVAL;
+    g_last_error[0] = 0;
+    for (uint32_t m = 0; m < n; ++m) {
+        if (in->start[m] > c->j_n || in->size[m] > c->j_n - in->start[m]) {
+            std::snprintf(g_last_error, sizeof(g_last_error),
+                          "kdtn_remote_ingest: body %u reaches past the uploaded %llu bytes", m, (unsigned long long)c->j_n);
+            return KDTN_EINVAL;
+        }
+    }
+    for (uint32_t i = 0; i < nv; ++i) {
+        if (in->vni_ns.offs[i + 1] < in->vni_ns.offs[i] || (!in->vni_ns.bytes && in->vni_ns.offs[nv])) {
+            std::snprintf(g_last_error, sizeof(g_last_error), "kdtn_remote_ingest: vni_ns offsets must ascend");
+            return KDTN_EINVAL;
+        }
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    c->ri_done = false;
+    const uint32_t cap = next_pow2(2ull * nv);               // a power of two >= 2 n_vni (and >= 64)
+    uint32_t bits = 0;
+    while ((1u << bits) < cap) ++bits;
+    StreamsDrain drain{s, s};                                // (the copies below read caller memory)
+    TRY(upload(c, c->ri_start, in->start, (size_t)n * 8));
+    TRY(upload(c, c->ri_size, in->size, (size_t)n * 4));
+    TRY(upload(c, c->ri_vni, in->vni, (size_t)nv * 4));
+    TRY(upload(c, c->ri_nso, in->vni_ns.offs, nv ? ((size_t)nv + 1) * 4 : 0));
+    TRY(upload(c, c->ri_nsb, in->vni_ns.bytes, nv ? in->vni_ns.offs[nv] : 0));
+    TRY(ensure(c->ri_slots, (size_t)cap * 4));
+    TRY(ensure(c->ri_plan, (size_t)n * sizeof(kdtn_remote_plan)));
+    TRY(ensure(c->ri_qd, (size_t)n * sizeof(kdtn_qdisc)));
+    TRY(ensure(c->ri_ctl, RP_CTL_WORDS * 4));
+    HIP_TRY(hipMemsetAsync(c->ri_slots.p, 0xFF, (size_t)cap * 4, s));
+    HIP_TRY(hipMemsetAsync(c->ri_ctl.p, 0, RP_CTL_WORDS * 4, s));
+    c->n_ev = 0;
+    (void)hipEventRecord(c->ev[0], s);
+    if (nv) k_rp_vni_build<<<nblocks(nv), BLOCK, 0, s>>>(dp<int32_t>(c->ri_vni), nv, dp<uint32_t>(c->ri_slots), cap - 1, 32u - bits);
+    timer_mark(c, "rp_vni_build");
+    const RpIn ri{dp<uint8_t>(c->j_doc), n, dp<uint64_t>(c->ri_start), dp<uint32_t>(c->ri_size), nv, dp<int32_t>(c->ri_vni),
+                  dp<uint8_t>(c->ri_nsb), dp<uint32_t>(c->ri_nso), dp<uint32_t>(c->ri_slots), cap - 1, 32u - bits,
+                  c->cfg.tick_in_usec};
+    if (n) k_rp_plan<<<nblocks(n, 64), UW_BLOCK, 0, s>>>(ri, dp<uint4>(c->ri_plan), qdisc ? dp<uint2>(c->ri_qd) : nullptr,
+                                                        dp<uint32_t>(c->ri_ctl));
+    timer_mark(c, "rp_plan");
+    HIP_TRY(hipGetLastError());
+    uint32_t ctl[RP_CTL_WORDS] = {};
+    TRY(d2h(c, ctl, c->ri_ctl.p, RP_CTL_WORDS));
+    if (n) HIP_TRY(hipMemcpyAsync(plan, c->ri_plan.p, (size_t)n * sizeof(kdtn_remote_plan), hipMemcpyDeviceToHost, s));
+    if (n && qdisc) HIP_TRY(hipMemcpyAsync(qdisc, c->ri_qd.p, (size_t)n * sizeof(kdtn_qdisc), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    drain.armed = false;
+    c->ri_report = kdtn_remote_ingest_plan_t{UW_WIN, ctl[RP_CTL_DIRECT], ctl[RP_CTL_REJECTED], ctl[RP_CTL_CONFLICT]};
+    c->ri_done = true;
+    return KDTN_OK;
+}
+
+int kdtn_remote_ingest_plan(kdtn_ctx* c, kdtn_remote_ingest_plan_t* out) {
+    if (!c || !out || !c->ri_done) return KDTN_EINVAL;
+    *out = c->ri_report;
     return KDTN_OK;
 }
 

@@ -870,6 +870,25 @@ __global__ void k_uw_pods(UwIn in, UwFrames f, JsTopoOut to, JsIntern it);
 __global__ void k_uw_counts(UwIn in, UwFrames f, uint32_t* cdes, uint32_t* creal, uint8_t* err8);
 __global__ void k_uw_offsets(UwIn in, const uint64_t* des64, const uint64_t* real64, JsTopoOut to, uint32_t* rbase);
 
+// ---- RemotePod bodies → Remote.Update plans (kdtn_remote.hip) -------------------------------
+constexpr uint32_t RP_EMPTY = 0xFFFFFFFFu;   // a free slot of the VNI table; "no entry" of a lookup
+enum : int { RP_CTL_DIRECT = 0, RP_CTL_REJECTED = 1, RP_CTL_CONFLICT = 2, RP_CTL_WORDS = 4 };   // the report block
+struct RpIn {
+    const uint8_t* doc;        // the receive buffer, padded past its end (kdtn_json_upload)
+    uint32_t n_msgs;
+    const uint64_t* start;     // [n_msgs] body m = doc[start[m], start[m] + size[m])
+    const uint32_t* size;
+    uint32_t n_vni;            // the VxlanManager snapshot: vni, the netns it is stored with
+    const int32_t* vni;
+    const uint8_t* ns_bytes;
+    const uint32_t* ns_offs;   // [n_vni + 1]
+    const uint32_t* slots;     // the table k_rp_vni_build made: vmask + 1 slots, home = hash >> vshift
+    uint32_t vmask, vshift;
+    double tick;               // tick_in_usec, for time2Tick
+};
+__global__ void k_rp_vni_build(const int32_t* vni, uint32_t n, uint32_t* slots, uint32_t mask, uint32_t shift);
+__global__ void k_rp_plan(RpIn in, uint4* plan, uint2* qdisc, uint32_t* ctl);
+
 // sharded ingest (kdtn_json_ingest_shard): keep[t] = this shard owns topology t; then the
 // kept topologies' columns and records compacted into fresh tables (document order kept)
 __global__ void k_shard_mark(DevTopos T, const uint8_t* kd_bytes, const uint32_t* kd_offs, uint32_t nshards,

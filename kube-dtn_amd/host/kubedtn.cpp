@@ -270,6 +270,51 @@ std::vector<Qdiscs> MakeQdiscs(Engine& e, const std::vector<LinkProperties>& pro
     return out;
 }
 
+std::vector<RemoteUpdatePlan> Update(Engine& e, const std::vector<std::string>& bodies,
+                                     const std::vector<std::pair<int32_t, std::string>>& vxlan) {
+    const uint32_t n = (uint32_t)bodies.size(), nv = (uint32_t)vxlan.size();
+    std::string buf, ns;
+    std::vector<uint64_t> start(n);
+    std::vector<uint32_t> size(n), ns_offs(nv + 1, 0);
+    std::vector<int32_t> vni(nv);
+    for (uint32_t m = 0; m < n; ++m) {
+        start[m] = buf.size();
+        size[m] = (uint32_t)bodies[m].size();
+        buf += bodies[m];
+    }
+    for (uint32_t i = 0; i < nv; ++i) {
+        vni[i] = vxlan[i].first;
+        ns += vxlan[i].second;
+        ns_offs[i + 1] = (uint32_t)ns.size();
+    }
+    if (int rc = kdtn_json_upload(e.ctx(), reinterpret_cast<const uint8_t*>(buf.data()), buf.size())) fail("kdtn_json_upload", rc);
+    kdtn_remote_in in{};
+    in.n_msgs = n;
+    in.start = start.data();
+    in.size = size.data();
+    in.n_vni = nv;
+    in.vni = vni.data();
+    in.vni_ns = kdtn_strtab{reinterpret_cast<const uint8_t*>(ns.data()), ns_offs.data(), nv};
+    std::vector<kdtn_remote_plan> plan(n);
+    std::vector<kdtn_qdisc> q(n);
+    if (int rc = kdtn_remote_ingest(e.ctx(), &in, plan.data(), q.data())) fail("kdtn_remote_ingest", rc);
+    std::vector<RemoteUpdatePlan> out(n);
+    for (uint32_t m = 0; m < n; ++m) {
+        const kdtn_remote_plan& p = plan[m];
+        RemoteUpdatePlan& r = out[m];
+        r.wire_err = p.wire_err;
+        if (p.wire_err) continue;
+        std::string* const field[KDTN_RP_NSTR] = {&r.NetNs, &r.IntfName, &r.IntfIp, &r.PeerVtep, &r.KubeNs, &r.Name};
+        for (int k = 0; k < KDTN_RP_NSTR; ++k) field[k]->assign(buf, p.str[k].off, p.str[k].len);
+        r.Vni = p.vni;
+        r.vni_conflict = p.vni_conflict != 0;
+        if (r.vni_conflict) r.conflict_netns = vxlan[p.vni_entry].second;
+        r.err = p.err;
+        r.qdiscs = to_qdiscs(q[m]);
+    }
+    return out;
+}
+
 BatchResponse BatchOutcome(const std::vector<LinkPlan>& plans) {
     BatchResponse r;
     for (size_t i = 0; i < plans.size(); ++i) {

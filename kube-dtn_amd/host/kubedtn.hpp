@@ -19,6 +19,7 @@
 #include <optional>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/kdtn.h"
@@ -122,6 +123,22 @@ class TopologyReconciler {
 
 // common.MakeQdiscs for a batch of property sets (one GPU launch).
 std::vector<Qdiscs> MakeQdiscs(Engine& e, const std::vector<LinkProperties>& props);
+
+// Pure prefix of KubeDTN.Update (daemon/kubedtn/handler.go:149-198) for one Remote.Update call.
+struct RemoteUpdatePlan {
+    int wire_err = KDTN_WIRE_OK;   // proto.Unmarshal's failure (kdtn_wire_err); the rest is then empty
+    std::string NetNs, IntfName, IntfIp, PeerVtep, KubeNs, Name;     // pb.RemotePod
+    int32_t Vni = 0;
+    bool vni_conflict = false;     // :177-185 an existing VXLAN with this VNI in another netns
+    std::string conflict_netns;    // the netns RemoveLinkWithVni is called with
+    int err = KDTN_E_NONE;         // KDTN_E_REMOTE_CIDR, else the first failing MakeQdiscs step
+    Qdiscs qdiscs;                 // MakeQdiscs(pod.Properties)
+};
+
+// KubeDTN.Update for a batch of request bodies (serialized pb.RemotePod, as the gRPC server hands
+// them over), each planned against the VxlanManager map as it is when the batch starts.
+std::vector<RemoteUpdatePlan> Update(Engine& e, const std::vector<std::string>& bodies,
+                                     const std::vector<std::pair<int32_t, std::string>>& vxlan = {});
 
 // Daemon handlers' batch semantics over the plans of one LinksBatchQuery.
 BatchResponse BatchOutcome(const std::vector<LinkPlan>& plans);

@@ -185,6 +185,28 @@ class WirePlan(C.Structure):
                                           "n_pod_frames", "n_rejected", "intern_passes", "reserved")]
 
 
+# kdtn_remote_plan.str columns (RemotePod fields 1-5, 8)
+RP_NET_NS, RP_INTF_NAME, RP_INTF_IP, RP_PEER_VTEP, RP_KUBE_NS, RP_NAME, RP_NSTR = range(7)
+RP_NO_ENTRY = 0xFFFFFFFF                       # kdtn_remote_plan.vni_entry: the snapshot has no such vni
+
+
+class RemoteIn(C.Structure):
+    _fields_ = [("n_msgs", C.c_uint32), ("start", C.c_void_p), ("size", C.c_void_p), ("n_vni", C.c_uint32),
+                ("vni", C.c_void_p), ("vni_ns", Strtab)]
+
+
+class RemoteIngestPlan(C.Structure):
+    """kdtn_remote_ingest_plan_t: what the last kdtn_remote_ingest did."""
+    _fields_ = [(f, C.c_uint32) for f in ("window_bytes", "n_direct", "n_rejected", "n_conflict")]
+
+
+REMOTE_PLAN_DTYPE = np.dtype([("str", np.dtype([("off", np.uint32), ("len", np.uint32)]), (RP_NSTR,)),
+                              ("vni", np.int32), ("vni_entry", np.uint32), ("wire_err", np.uint8),
+                              ("err", np.uint8), ("vni_conflict", np.uint8), ("has_props", np.uint8),
+                              ("reserved", np.uint32)])
+assert REMOTE_PLAN_DTYPE.itemsize == 64
+
+
 class IngestInfo(C.Structure):
     _fields_ = [("n_topos", C.c_uint32), ("n_desired", C.c_uint32), ("n_realised", C.c_uint32),
                 ("n_kdict", C.c_uint32), ("n_pdict", C.c_uint32), ("json_err", C.c_int32),
@@ -235,7 +257,7 @@ EXPORTS = ["kdtn_version", "kdtn_strerror", "kdtn_err_name", "kdtn_init", "kdtn_
            "kdtn_vni_ops_export", "kdtn_vni_ops_import", "kdtn_json_ingest_delta",
            "kdtn_epoch_download_async", "kdtn_epoch_download_wait", "kdtn_epoch_late_pods",
            "kdtn_epoch_plan", "kdtn_epoch_status_encode", "kdtn_epoch_download_status",
-           "kdtn_wire_ingest", "kdtn_wire_ingest_plan"]
+           "kdtn_wire_ingest", "kdtn_wire_ingest_plan", "kdtn_remote_ingest", "kdtn_remote_ingest_plan"]
 
 
 def ptr(a: np.ndarray, t):

@@ -121,6 +121,8 @@ def lib() -> C.CDLL:
         "kdtn_epoch_download_status": (C.c_int, [vp, C.POINTER(abi.StatusJson)]),
         "kdtn_wire_ingest": (C.c_int, [vp, C.POINTER(abi.WireIn), C.POINTER(abi.IngestInfo)]),
         "kdtn_wire_ingest_plan": (C.c_int, [vp, C.POINTER(abi.WirePlan)]),
+        "kdtn_remote_ingest": (C.c_int, [vp, C.POINTER(abi.RemoteIn), vp, vp]),
+        "kdtn_remote_ingest_plan": (C.c_int, [vp, C.POINTER(abi.RemoteIngestPlan)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -412,6 +414,36 @@ class Engine:
         """What the last wire_ingest did (kdtn_wire_ingest_plan)."""
         p = abi.WirePlan()
         _check(lib().kdtn_wire_ingest_plan(self._ctx, C.byref(p)), "kdtn_wire_ingest_plan")
+        return p
+
+    def remote_ingest(self, stream: bytes, start, size, vni=None, vni_ns=None):
+        """kdtn_remote_ingest: RemotePod request bodies (body m = stream[start[m], start[m] +
+        size[m])) decoded and planned on the GPU against the VxlanManager snapshot vni[i] →
+        vni_ns[i] (netns as bytes or str). Returns (plan, qdisc): abi.REMOTE_PLAN_DTYPE and
+        abi.QDISC_DTYPE arrays, one record per message."""
+        start = np.ascontiguousarray(start, dtype=np.uint64)
+        size = np.ascontiguousarray(size, dtype=np.uint32)
+        if len(start) != len(size):
+            raise ValueError("start and size must have one entry per message")
+        vni = np.ascontiguousarray([] if vni is None else vni, dtype=np.int32)
+        ns = [s.encode() if isinstance(s, str) else bytes(s) for s in ([] if vni_ns is None else vni_ns)]
+        if len(ns) != len(vni):
+            raise ValueError("vni_ns must hold one netns per vni")
+        ns_bytes = np.frombuffer(b"".join(ns) + b"\0", np.uint8)
+        ns_offs = np.cumsum([0] + [len(s) for s in ns]).astype(np.uint32)
+        self.json_upload(bytes(stream))
+        n = len(size)
+        plan, qdisc = np.zeros(max(n, 1), abi.REMOTE_PLAN_DTYPE), np.zeros(max(n, 1), abi.QDISC_DTYPE)
+        rin = abi.RemoteIn(n, start.ctypes.data if n else None, size.ctypes.data if n else None, len(vni),
+                           vni.ctypes.data if len(vni) else None,
+                           abi.Strtab(abi.ptr(ns_bytes, abi.u8p), abi.ptr(ns_offs, abi.u32p), len(vni)))
+        _check(lib().kdtn_remote_ingest(self._ctx, C.byref(rin), plan.ctypes.data, qdisc.ctypes.data), "kdtn_remote_ingest")
+        return plan[:n], qdisc[:n]
+
+    def remote_plan(self) -> abi.RemoteIngestPlan:
+        """What the last remote_ingest did (kdtn_remote_ingest_plan)."""
+        p = abi.RemoteIngestPlan()
+        _check(lib().kdtn_remote_ingest_plan(self._ctx, C.byref(p)), "kdtn_remote_ingest_plan")
         return p
 
     def ingest_doc_index(self) -> np.ndarray:
