@@ -917,7 +917,7 @@ typedef struct kdtn_plan {
     uint32_t n_cus;               /* compute units of the device                                */
     uint32_t nwg;                 /* chunks of 64 Topologies (k_reconcile workgroups / split)   */
     uint32_t front;               /* 0 serial launches, 1 fused (k_epoch_front + k_pdict_verify),
-                                   * 2 pod lookup tables on a side stream                       */
+                                   * (2: pod lookup tables on a side stream; no longer produced) */
     uint32_t diff_build;          /* 1: comparison build of k_reconcile (deferred emission,
                                    * then k_place_scan + k_place); 0: ticket + look-back build   */
     uint32_t split;               /* k_reconcile workgroups per chunk                           */
@@ -939,7 +939,7 @@ int kdtn_timer_totals(kdtn_ctx* ctx, const char** names, double* ms, uint32_t* e
 /* Per-workgroup phase timestamps of k_reconcile (100 MHz clock; 8 words per workgroup:
  * entry, topologies loaded, counts done, batch bases known, end, XCC_ID<<32|HW_ID, CalcDiff
  * window phase A done, phase B done) of the
- * last epoch run with KDTN_VARIANT bit 16 set. Returns the number of words copied. */
+ * last epoch run with the trace bit (value 16, bit 4) of KDTN_VARIANT set. Returns the number of words copied. */
 int kdtn_debug_wg_trace(kdtn_ctx* ctx, uint64_t* out, uint32_t cap);
 
 #ifdef __cplusplus

@@ -96,9 +96,6 @@ struct kdtn_ctx_handles {
     hipStream_t stream = nullptr;
     hipStream_t comm_stream = nullptr;          // RCCL pod-status exchange (nranks > 1)
     hipStream_t copy_stream = nullptr;          // delta uploads: host-to-device copies beside the kernels
-    hipStream_t side_stream = nullptr;          // the pod lookup build beside the dictionary parses
-    hipStream_t side_hi = nullptr;              // (profiling A/B: the same at the highest priority)
-    hipEvent_t ev_front = nullptr, ev_side = nullptr;
     hipEvent_t ev_cp[4] = {};
     hipEvent_t ev_col[LINK_COLS32 + 1] = {};   // a delta's staged column copies (+ uid), each placed on arrival
     hipStream_t d2h_stream = nullptr;           // kdtn_epoch_download_async: the outputs' copies

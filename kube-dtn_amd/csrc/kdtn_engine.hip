@@ -350,12 +350,11 @@ DevTopos topo_view(kdtn_ctx* c) {
     return t;
 }
 
-// Parse the property strings [p0, n): one thread per (string, interpretation) when split
-// (three launches' worth of waves in one grid), else one thread per string.
+// Parse the property strings [p0, n): one thread per (string, interpretation), three
+// launches' worth of waves in one grid (125k-pod config 2: 0.0374 -> 0.0341 ms against one
+// thread per string; 1M: equal).
 static void launch_pdict(kdtn_ctx* c, uint32_t p0, uint32_t n) {
-    bool split = KDTN_PD_SPLIT_DEFAULT;
 #if KDTN_PROFILING
-    if (const char* ev = std::getenv("KDTN_PD_SPLIT")) split = std::atoi(ev) != 0;
     if (const char* ev = std::getenv("KDTN_PD_ONLY")) {           // one interpretation alone (A/B)
         const int w = std::atoi(ev);
         auto one = [&](auto kern) {
@@ -367,17 +366,11 @@ static void launch_pdict(kdtn_ctx* c, uint32_t p0, uint32_t n) {
         if (w == PD_DUR) { one(k_pdict_only<PD_DUR>); return; }
         if (w == PD_PCT) { one(k_pdict_only<PD_PCT>); return; }
         if (w == PD_RATE) { one(k_pdict_only<PD_RATE>); return; }
-        if (w == (PD_RATE | PD_RATE_GENERIC)) { one(k_pdict_only<PD_RATE | PD_RATE_GENERIC>); return; }
     }
 #endif
-    const dim3 grid(nblocks(n - p0), split ? 3 : 1);
-    auto go = [&](auto kern) {
-        kern<<<grid, BLOCK, 0, c->stream>>>(dp<uint8_t>(c->pd_bytes), dp<uint32_t>(c->pd_offs), p0, n,
-                                            c->cfg.tick_in_usec, dp<uint32_t>(c->pd_pct), dp<uint2>(c->pd_dur),
-                                            dp<uint2>(c->pd_rate), dp<uint32_t>(c->pd_rerr));
-    };
-    if (split) go(k_pdict_parse<true>);
-    else go(k_pdict_parse<false>);
+    k_pdict_parse<<<dim3(nblocks(n - p0), 3), BLOCK, 0, c->stream>>>(
+        dp<uint8_t>(c->pd_bytes), dp<uint32_t>(c->pd_offs), p0, n, c->cfg.tick_in_usec, dp<uint32_t>(c->pd_pct),
+        dp<uint2>(c->pd_dur), dp<uint2>(c->pd_rate), dp<uint32_t>(c->pd_rerr));
 }
 
 // Special key-string ids (SPECIAL_DEFAULT / SPECIAL_LOCALHOST) at or past the parse start
@@ -819,15 +812,6 @@ int kdtn_init(kdtn_ctx** out, const kdtn_config* cfg) {
     for (hipEvent_t& e : c->ev_cp) (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);
     for (hipEvent_t& e : c->ev_col) (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);
     if (hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) != hipSuccess) c->copy_stream = nullptr;
-    if (hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking) != hipSuccess) c->side_stream = nullptr;
-    {
-        int lo = 0, hi = 0;
-        if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess ||
-            hipStreamCreateWithPriority(&c->side_hi, hipStreamNonBlocking, hi) != hipSuccess)
-            c->side_hi = nullptr;
-    }
-    if (hipEventCreateWithFlags(&c->ev_front, hipEventDisableTiming) != hipSuccess) c->ev_front = nullptr;
-    if (hipEventCreateWithFlags(&c->ev_side, hipEventDisableTiming) != hipSuccess) c->ev_side = nullptr;
     if (hipStreamCreateWithFlags(&c->d2h_stream, hipStreamNonBlocking) != hipSuccess) c->d2h_stream = nullptr;
     (void)hipEventCreateWithFlags(&c->ev_dl_ready, hipEventDisableTiming);
     (void)hipEventCreateWithFlags(&c->ev_dl_done, hipEventDisableTiming);
@@ -840,7 +824,7 @@ void kdtn_destroy(kdtn_ctx* c) {
     (void)hipSetDevice(c->device);
     (void)kdtn_epoch_download_wait(c);
     (void)hipStreamSynchronize(c->stream);
-    for (hipStream_t st : {c->comm_stream, c->copy_stream, c->side_stream, c->side_hi, c->d2h_stream})
+    for (hipStream_t st : {c->comm_stream, c->copy_stream, c->d2h_stream})
         if (st) (void)hipStreamSynchronize(st);
     // every stream is synchronised: the members (each DevBuf retires its memory) go first, then
     // the base's destructor frees the retired buffers and tears the handles down
@@ -863,10 +847,7 @@ kdtn_ctx_handles::~kdtn_ctx_handles() {
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ev_col)
         if (e) (void)hipEventDestroy(e);
-    for (hipStream_t st : {c->copy_stream, c->side_stream, c->side_hi})
-        if (st) (void)hipStreamDestroy(st);
-    if (c->ev_front) (void)hipEventDestroy(c->ev_front);
-    if (c->ev_side) (void)hipEventDestroy(c->ev_side);
+    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->d2h_stream) (void)hipStreamDestroy(c->d2h_stream);
     if (c->ev_dl_ready) (void)hipEventDestroy(c->ev_dl_ready);
     if (c->ev_dl_done) (void)hipEventDestroy(c->ev_dl_done);
@@ -1008,57 +989,31 @@ int kdtn_epoch_run(kdtn_ctx* c, uint32_t stages) {
     uint32_t* special = dp<uint32_t>(c->kd_special);
     const uint32_t n16 = (uint32_t)(sync_bytes(c->nwg) / 16);
     const uint32_t nbz = std::min<uint32_t>(nblocks(n16), 256);
-    // the pod lookup tables (scatter, then verify fused with the full-prefix scan) on a side
-    // stream beside the dictionary parses, which they do not need (the PHYSICAL bit of a pod's
-    // name comes from its bytes): the comm stream right after the RCCL all-gather, else
-    // side_stream after the first launch; k_reconcile waits for them
-#if KDTN_PROFILING
-    int side_mode = KDTN_LOOKUP_SIDE_DEFAULT;
-    if (const char* ev = std::getenv("KDTN_LOOKUP_SIDE")) side_mode = std::atoi(ev);
-#else
-    constexpr int side_mode = KDTN_LOOKUP_SIDE_DEFAULT;
-#endif
-    hipStream_t ls = exchange ? c->comm_stream : (side_mode == 2 && c->side_hi ? c->side_hi : c->side_stream);
-    const bool side = side_mode && !fused && resolve && pod_rows && !pods_cur && c->T && ls && c->ev_front && c->ev_side;
     c->plan = kdtn_plan{};
     c->plan.n_cus = c->n_cus;
     c->plan.nwg = c->nwg;
-    c->plan.front = fused ? 1u : side ? 2u : 0u;
+    c->plan.front = fused ? 1u : 0u;
     c->plan.kstrings_parsed = c->D - std::min(c->D, c->kd_from & ~63u);
     c->plan.pstrings_parsed = c->P - std::min(c->P, c->pd_from & ~63u);
-    // 4 pod rows per thread in the lookup build (every row load issued before the dependent
-    // accesses): rank of 8 0.1761 / 0.1770 → 0.1735 / 0.1744 ms, N = 1 0.7895 → 0.7883 ms
+    // POD_PER (4) pod rows per thread in the lookup build (every row load issued before the
+    // dependent accesses): rank of 8 0.1761 / 0.1770 → 0.1735 / 0.1744 ms, N = 1 0.7895 → 0.7883 ms
     // (profiles/r05h_pod_per_ab_*)
-#if KDTN_PROFILING
-    int pod_per = 4;                                                 // (A/B: KDTN_POD_PER = 1, 2, 4)
-    if (const char* ev = std::getenv("KDTN_POD_PER")) pod_per = std::atoi(ev);
-#else
-    constexpr int pod_per = 4;
-#endif
-    auto lookup_build = [&](hipStream_t q, bool parsed) -> int {
+    auto lookup_build = [&]() -> int {
         if (++c->pod_stamp >= 0x7FFFFFFFu) {                             // stamp wrap: clear once
-            HIP_TRY(hipMemsetAsync(c->pod_direct.p, 0, c->pod_direct.cap, q));
-            HIP_TRY(hipMemsetAsync(c->pod_ovf.p, 0, c->pod_ovf.cap, q));
+            HIP_TRY(hipMemsetAsync(c->pod_direct.p, 0, c->pod_direct.cap, s));
+            HIP_TRY(hipMemsetAsync(c->pod_ovf.p, 0, c->pod_ovf.cap, s));
             c->pod_stamp = 1;
         }
-        auto kern = pod_per == 4 ? k_pod_direct_scatter<4> : k_pod_direct_scatter<1>;
-#if KDTN_PROFILING
-        if (pod_per == 2) kern = k_pod_direct_scatter<2>;
-#endif
-        kern<<<nblocks(pod_rows, BLOCK * pod_per), BLOCK, 0, q>>>(
-            dp<uint4>(c->pods), pod_rows, parsed ? dp<uint32_t>(c->kd_bits) + (size_t)KB_PHYSICAL * c->kb_words : nullptr,
+        k_pod_direct_scatter<<<nblocks(pod_rows, BLOCK * POD_PER), BLOCK, 0, s>>>(
+            dp<uint4>(c->pods), pod_rows, dp<uint32_t>(c->kd_bits) + (size_t)KB_PHYSICAL * c->kb_words,
             dp<uint8_t>(c->kd_bytes), dp<uint32_t>(c->kd_offs), dp<uint4>(c->pod_direct), c->pod_stamp, c->D,
             c->pods_rank_major ? (uint32_t)c->nranks : 1u, c->pod_total);
         return KDTN_OK;
     };
-    auto verify_prefix = [&](hipStream_t q) {
-        const uint32_t nbv = nblocks(pod_rows, BLOCK * pod_per);
+    auto verify_prefix = [&]() {
+        const uint32_t nbv = nblocks(pod_rows, BLOCK * POD_PER);
         const uint32_t nbp = (uint32_t)std::min<uint64_t>(4 * FP_GRID, (c->T + 4 * BLOCK - 1) / (4 * BLOCK));
-        auto kern = pod_per == 4 ? k_pod_verify_prefix<4> : k_pod_verify_prefix<1>;
-#if KDTN_PROFILING
-        if (pod_per == 2) kern = k_pod_verify_prefix<2>;
-#endif
-        kern<<<nbv + std::max<uint32_t>(nbp, 1), BLOCK, 0, q>>>(
+        k_pod_verify_prefix<<<nbv + std::max<uint32_t>(nbp, 1), BLOCK, 0, s>>>(
             dp<uint4>(c->pods), pod_rows, dp<uint4>(c->pod_direct), c->pod_stamp,
             dp<unsigned long long>(c->pod_ovf), c->ovf_mask, c->D, T, sync + SYNC_FIRST_PARTIAL_INV, nbv,
             c->pods_rank_major ? (uint32_t)c->nranks : 1u, c->pod_total);
@@ -1103,7 +1058,6 @@ int kdtn_epoch_run(kdtn_ctx* c, uint32_t stages) {
             k_epoch_begin<<<nbz + nblocks(fill), BLOCK, 0, q>>>(reinterpret_cast<uint4*>(sync), n16, nbz, T, fill,
                                                                 rank_base, dp<uint4>(c->pods));
         };
-        const bool begin_first = side && !exchange;                 // (A/B: the lookup build waits for it)
         if (exchange) {
             HIP_TRY(hipEventRecord(c->ev_fill, s));                   // after the previous epoch's kernels
             HIP_TRY(hipStreamWaitEvent(c->comm_stream, c->ev_fill, 0));
@@ -1116,98 +1070,44 @@ int kdtn_epoch_run(kdtn_ctx* c, uint32_t stages) {
                 return KDTN_EIO;
             }
             HIP_TRY(hipEventRecord(c->ev_ag, c->comm_stream));
-        } else if (begin_first) {
-            begin(s);
-            timer_mark(c, "pods_fill", 2);
-        }
-        if (side) {
-            if (!exchange) {
-                HIP_TRY(hipEventRecord(c->ev_front, s));
-                HIP_TRY(hipStreamWaitEvent(ls, c->ev_front, 0));
-            }
-            TRY(lookup_build(ls, false));
-            verify_prefix(ls);
-            HIP_TRY(hipEventRecord(c->ev_side, ls));
         }
         // dictionaries: the strings this upload added (all of them unless kdict_keep /
         // pdict_keep), from a multiple of 64 so every wave writes whole predicate words
-        uint32_t* special = dp<uint32_t>(c->kd_special);
+        const uint32_t k0 = c->kd_from & ~63u;                            // (clip_specials ran at upload)
+        if (c->D > k0) {
+            const uint8_t* kb = dp<uint8_t>(c->kd_bytes);
+            const uint32_t* ko = dp<uint32_t>(c->kd_offs);
+            uint32_t* bits = dp<uint32_t>(c->kd_bits);
+            const uint32_t nk = c->D - k0;
+            auto kern = k_kdict_flags;
 #if KDTN_PROFILING
-        int dict_fuse = KDTN_DICT_FUSE_DEFAULT ? 1 : 0;
-        if (const char* ev = std::getenv("KDTN_DICT_FUSE")) dict_fuse = std::atoi(ev);
-#else
-        constexpr int dict_fuse = KDTN_DICT_FUSE_DEFAULT ? 1 : 0;
-#endif
-        const uint32_t k0f = c->kd_from & ~63u, p0f = c->pd_from & ~63u;
-        if (dict_fuse && c->D > k0f && c->P > p0f) {              // both parses in one launch
-            const uint32_t nbk = nblocks(c->D - k0f), nbp = nblocks(c->P - p0f);
-            auto kern = k_dict_parse;
-#if KDTN_PROFILING
-            if (dict_fuse >= 3) kern = k_dict_parse_w7;                  // (3: values first, 4: keys first)
-#endif
-            kern<<<3 * nbp + nbk, BLOCK, 0, s>>>(
-                dp<uint8_t>(c->kd_bytes), dp<uint32_t>(c->kd_offs), k0f, c->D, dp<uint32_t>(c->kd_bits), c->kb_words,
-                special, dp<uint8_t>(c->pd_bytes), dp<uint32_t>(c->pd_offs), p0f, c->P, nbp, c->cfg.tick_in_usec,
-                dp<uint32_t>(c->pd_pct), dp<uint2>(c->pd_dur), dp<uint2>(c->pd_rate), dp<uint32_t>(c->pd_rerr),
-                (dict_fuse == 2 || dict_fuse == 4) ? nbk : 0u);
-            timer_mark(c, "dict_parse", 2);
-        } else {
-        {
-            const uint32_t k0 = c->kd_from & ~63u;                        // (clip_specials ran at upload)
-            if (c->D > k0) {
-                const uint8_t* kb = dp<uint8_t>(c->kd_bytes);
-                const uint32_t* ko = dp<uint32_t>(c->kd_offs);
-                uint32_t* bits = dp<uint32_t>(c->kd_bits);
-                const uint32_t nk = c->D - k0;
-    #if KDTN_PROFILING
-                int sub = 1;                                               // strings per thread (2, 4: slower)
-                if (const char* ev = std::getenv("KDTN_KD_SUB")) sub = std::atoi(ev);
-                if (sub == 4) k_kdict_flags<4, false, BLOCK><<<nblocks(nk, BLOCK * 4), BLOCK, 0, s>>>(kb, ko, k0, c->D, bits, c->kb_words, special);
-                else if (sub == 2) k_kdict_flags<2, false, BLOCK><<<nblocks(nk, BLOCK * 2), BLOCK, 0, s>>>(kb, ko, k0, c->D, bits, c->kb_words, special);
-                else if (sub == 8) k_kdict_flags<1, true, BLOCK><<<nblocks(nk), BLOCK, 0, s>>>(kb, ko, k0, c->D, bits, c->kb_words, special);
-                else if (sub == 16) k_kdict_flags_ws<<<nblocks(nk), BLOCK, 0, s>>>(kb, ko, k0, c->D, bits, c->kb_words, special);
-                else if (sub >= 32 && sub < 40) {
-                    const uint32_t nb = std::min(nblocks(nk), (uint32_t)(c->n_cus * 8 * (sub - 31)));
-                    k_kdict_flags_pp<<<nb, BLOCK, 0, s>>>(kb, ko, k0, c->D, bits, c->kb_words, special);
-                }
-                else if (sub == 40) k_kdict_null<<<nblocks(nk), BLOCK, 0, s>>>(kb, ko, k0, c->D, bits, c->kb_words, special);
-                else if (sub == 42) k_kdict_flags_v1<<<nblocks(nk), BLOCK, 0, s>>>(kb, ko, k0, c->D, bits, c->kb_words, special);
-                else if (sub == 41) k_kdict_loadonly<<<nblocks(nk), BLOCK, 0, s>>>(kb, ko, k0, c->D, bits, c->kb_words, special);
-                else if (sub == 64) k_kdict_flags<1, false, 64><<<nblocks(nk, 64), 64, 0, s>>>(kb, ko, k0, c->D, bits, c->kb_words, special);
-                else if (sub == 1024) k_kdict_flags<1, false, 1024><<<nblocks(nk, 1024), 1024, 0, s>>>(kb, ko, k0, c->D, bits, c->kb_words, special);
-                else
-    #endif
-                k_kdict_flags<1, false, BLOCK><<<nblocks(nk), BLOCK, 0, s>>>(kb, ko, k0, c->D, bits, c->kb_words, special);
+            if (const char* ev = std::getenv("KDTN_KD_SUB")) {            // the kernel's floors (wrong tables)
+                const int sub = std::atoi(ev);
+                if (sub == 40) kern = k_kdict_null;
+                else if (sub == 41) kern = k_kdict_loadonly;
             }
+#endif
+            kern<<<nblocks(nk), BLOCK, 0, s>>>(kb, ko, k0, c->D, bits, c->kb_words, special);
         }
         timer_mark(c, "kdict_parse", 2);
-        {
-            const uint32_t p0 = c->pd_from & ~63u;
-            if (c->P > p0) launch_pdict(c, p0, c->P);
-        }
+        const uint32_t p0 = c->pd_from & ~63u;
+        if (c->P > p0) launch_pdict(c, p0, c->P);
         timer_mark(c, "pdict_parse", 2);
-        }
-        if (!exchange && !begin_first) {
+        if (!exchange) {
             begin(s);
             timer_mark(c, "pods_fill", 2);
         }
         if (resolve) {
-            if (side) {
-                if (c->V) TRY(build_vni_table(c));
-                HIP_TRY(hipStreamWaitEvent(s, c->ev_side, 0));             // lookup tables not hidden by the parses
-                timer_mark(c, "lookup_wait", 2);
-            } else {
-                if (exchange) HIP_TRY(hipStreamWaitEvent(s, c->ev_ag, 0));   // exchange not hidden by the parses
-                timer_mark(c, "pods_allgather", 2);
-                if (pod_rows && !pods_cur) TRY(lookup_build(s, true));
-                else if (!pods_cur && ++c->pod_stamp >= 0x7FFFFFFFu) {     // (no rows: the stamp still moves)
-                    HIP_TRY(hipMemsetAsync(c->pod_direct.p, 0, c->pod_direct.cap, s));
-                    HIP_TRY(hipMemsetAsync(c->pod_ovf.p, 0, c->pod_ovf.cap, s));
-                    c->pod_stamp = 1;
-                }
-                if (c->V) TRY(build_vni_table(c));
-                timer_mark(c, "hash_build", 2);
+            if (exchange) HIP_TRY(hipStreamWaitEvent(s, c->ev_ag, 0));   // exchange not hidden by the parses
+            timer_mark(c, "pods_allgather", 2);
+            if (pod_rows && !pods_cur) TRY(lookup_build());
+            else if (!pods_cur && ++c->pod_stamp >= 0x7FFFFFFFu) {     // (no rows: the stamp still moves)
+                HIP_TRY(hipMemsetAsync(c->pod_direct.p, 0, c->pod_direct.cap, s));
+                HIP_TRY(hipMemsetAsync(c->pod_ovf.p, 0, c->pod_ovf.cap, s));
+                c->pod_stamp = 1;
             }
+            if (c->V) TRY(build_vni_table(c));
+            timer_mark(c, "hash_build", 2);
         }
     }
     c->kd_valid = c->D;
@@ -1261,7 +1161,6 @@ int kdtn_epoch_run(kdtn_ctx* c, uint32_t stages) {
         w.m_cap = c->real.n;
         w.n_cap = c->des.n;
         uint32_t* wbase = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(w.wcount) + align_up((size_t)c->nwg * 12, 16));
-        bool placed = false;                                        // VAR_DIFF: k_place_scan + k_place
         // several workgroups per chunk when the chunks would not fill the chip about six times
         // over (4 resident k_reconcile workgroups per CU): they share a bulk chunk's records,
         // at least ~300 records per part (measured: 125k-pod config 2, 640 records per chunk:
@@ -1279,9 +1178,9 @@ int kdtn_epoch_run(kdtn_ctx* c, uint32_t stages) {
 #if KDTN_PROFILING
         if (const char* ev = std::getenv("KDTN_SPLIT")) if (std::atoi(ev) > 0) w.split = (uint32_t)std::atoi(ev);
 #endif
-        if (fused || side) {                            // verify + prefix ran in k_pdict_verify / on the side stream
+        if (fused) {                                     // verify + prefix ran in k_pdict_verify
         } else if (resolve && pod_rows && !pods_cur) {   // the pod-table verify with the full-prefix scan
-            verify_prefix(s);
+            verify_prefix();
             timer_mark(c, "verify_prefix", 2);
         } else {
             k_full_prefix<<<(unsigned)std::min<uint64_t>(FP_GRID, (c->T + 4 * FP_BLOCK - 1) / (4 * FP_BLOCK)), FP_BLOCK, 0, s>>>(
@@ -1289,8 +1188,9 @@ int kdtn_epoch_run(kdtn_ctx* c, uint32_t stages) {
             timer_mark(c, "full_prefix", 2);
         }
         if (c->timing == 1) (void)hipEventRecord(c->ev[0], s);
+        // CalcDiff windows (both lists non-empty): the comparison-heavy build
+        int variant = (c->real.n && c->des.n) ? DIFF_VARIANT : DEFAULT_VARIANT;
 #if KDTN_PROFILING
-        int variant = DEFAULT_VARIANT;
         if (const char* ev = std::getenv("KDTN_VARIANT")) variant = std::atoi(ev);
         if (variant & VAR_TRACE) {
             w.split = 1;                                           // trace slots per chunk
@@ -1298,32 +1198,29 @@ int kdtn_epoch_run(kdtn_ctx* c, uint32_t stages) {
             w.trace = reinterpret_cast<unsigned long long*>(c->trace.p);
             c->traced = true;
         }
+#endif
+        const bool placed = (variant & VAR_DIFF) != 0;           // deferred chunks, then k_place_scan + k_place
+        if (placed && ((size_t)c->real.n * 2 > c->del_idx.cap / 4 || (size_t)c->des.n * 2 > c->add_idx.cap / 4)) {
+            std::snprintf(g_last_error, sizeof(g_last_error), "deferred placement without upper halves");
+            return KDTN_EINVAL;
+        }
         switch (variant) {
 #define KDTN_VARIANT_CASE(V) \
-        case V: k_reconcile<V><<<c->nwg * w.split, BLOCK, 0, s>>>(T, c->real.view, c->des.view, tb, o, w); placed = (V & VAR_DIFF) != 0; break;
-        KDTN_PROFILING_VARIANTS(KDTN_VARIANT_CASE)
+        case V: k_reconcile<V><<<c->nwg * w.split, BLOCK, 0, s>>>(T, c->real.view, c->des.view, tb, o, w); break;
+        KDTN_VARIANT_CASE(DEFAULT_VARIANT)
         KDTN_VARIANT_CASE(DIFF_VARIANT)
+#if KDTN_PROFILING
+        KDTN_PROFILING_VARIANTS(KDTN_VARIANT_CASE)
+#endif
 #undef KDTN_VARIANT_CASE
         default:
-            k_reconcile<DEFAULT_VARIANT><<<c->nwg * w.split, BLOCK, 0, s>>>(T, c->real.view, c->des.view, tb, o, w);
-            break;
+            std::snprintf(g_last_error, sizeof(g_last_error), "k_reconcile variant %d is not instantiated", variant);
+            return KDTN_EINVAL;
         }
-#else
-        if (c->real.n && c->des.n) {             // CalcDiff windows: the comparison-heavy build
-            k_reconcile<DIFF_VARIANT><<<c->nwg * w.split, BLOCK, 0, s>>>(T, c->real.view, c->des.view, tb, o, w);
-            placed = true;
-        } else {
-            k_reconcile<DEFAULT_VARIANT><<<c->nwg * w.split, BLOCK, 0, s>>>(T, c->real.view, c->des.view, tb, o, w);
-        }
-#endif
         timer_mark(c, "reconcile", 1);
         c->plan.diff_build = placed ? 1u : 0u;
         c->plan.split = w.split;
         if (placed) {
-            if ((size_t)c->real.n * 2 > c->del_idx.cap / 4 || (size_t)c->des.n * 2 > c->add_idx.cap / 4) {
-                std::snprintf(g_last_error, sizeof(g_last_error), "deferred placement without upper halves");
-                return KDTN_EINVAL;
-            }
             k_place_scan<<<1, PLACE_SCAN_BLOCK, 0, s>>>(w.wcount, c->nwg, wbase, o, c->T);
             timer_mark(c, "place_scan", 1);
             if (c->nwg >= 4u * c->n_cus) {               // enough chunks for a wave each

@@ -20,7 +20,7 @@
 //   k_pdict_parse   ParseDuration / ParseFloatPercentage / ParseRate      (P threads)
 //   k_pods_fill     this rank's pod-status slice                          (slice threads)
 //   [RCCL all-gather of the pod-status table when nranks > 1]
-//   k_pod_direct_scatter + k_pod_direct_verify, k_vni_pack + k_vni_ht_build
+//   k_pod_direct_scatter + k_pod_verify_prefix, k_vni_pack + k_vni_ht_build
 //   k_reconcile     ONE pass per workgroup of TPW topologies: Reconcile gate + CalcDiff in
 //                   LDS, decoupled look-back for the batch bases, then barrier-free emission
 //                   of the batch lists, addLink/delLink/UpdateLinks pure prefix, MakeQdiscs.
@@ -109,82 +109,48 @@ struct DevLinks {
 };
 
 // Profiling build (make -C kube-dtn_amd prof → prof/libkdtn_prof.so, -DKDTN_PROFILING=1):
-// the A/B variants below are instantiated and selected from KDTN_VARIANT / KDTN_KD_SUB /
-// KDTN_JS_VARIANT. The product library (kdtn/libkdtn.so) compiles only DEFAULT_VARIANT and
-// the parity-tested paths, and reads no environment variable.
+// the measurement variants below are instantiated and selected from KDTN_VARIANT / KDTN_KD_SUB /
+// KDTN_JS_VARIANT. The product library (kdtn/libkdtn.so) compiles only DEFAULT_VARIANT,
+// DIFF_VARIANT and the parity-tested paths, and reads no environment variable. Both builds
+// launch the same variant unless KDTN_VARIANT names another.
 #ifndef KDTN_PROFILING
 #define KDTN_PROFILING 0
 #endif
-// epoch front: the pod lookup build (scatter, verify + full-prefix scan) on a side stream (the
-// comm stream after the all-gather when RCCL exchanges the rows) beside the dictionary parses
-#ifndef KDTN_LOOKUP_SIDE_DEFAULT
-#define KDTN_LOOKUP_SIDE_DEFAULT 0
-#endif
-// epoch front: k_kdict_flags and k_pdict_parse as one launch (k_dict_parse)
-#ifndef KDTN_DICT_FUSE_DEFAULT
-#define KDTN_DICT_FUSE_DEFAULT false    // A/B in one process: N = 1 0.797 vs 0.811 ms, N = 8 0.183 vs 0.185 (r05e)
-#endif
-// k_pdict_parse: one thread per (string, interpretation) instead of one per string
-#ifndef KDTN_PD_SPLIT_DEFAULT
-#define KDTN_PD_SPLIT_DEFAULT true    // 125k-pod config 2: 0.0374 -> 0.0341 ms; 1M: equal
-#endif
-// Emission variants (A/B in the profiling build; the product runs DEFAULT_VARIANT):
-//   bit 0: non-temporal streaming loads of link columns
-//   bit 1: non-temporal output stores
-//   bit 2: (profiling) compute MakeQdiscs but do not store it
-//   bit 3: non-temporal pod-slot gathers
-//   bit 4: (profiling) per-workgroup phase timestamps into RecWork::trace
-//   bits 5, 6: (profiling, wrong results) skip the pod-slot / percentage-table gathers
-//   bits 7, 8: occupancy target of 5 / 6 waves per SIMD (register budget 96 / 80 VGPRs)
-//   bit 9: parsed-table gathers only for non-empty property ids (id 0 = "" parses to 0)
-//   bit 10: (A/B) always run the look-back, ignoring k_full_prefix
-//   bit 11: comparison-heavy build (product): CalcDiff windows dominate (realised lists are
+// k_reconcile variant bits (the product runs DEFAULT_VARIANT or DIFF_VARIANT):
+//   value 1: non-temporal streaming loads of link columns
+//   value 2: non-temporal output stores
+//   value 4: (profiling) compute MakeQdiscs but do not store it
+//   value 16: (profiling) per-workgroup phase timestamps into RecWork::trace
+//   values 32, 64: (profiling, wrong results) skip the pod-slot / percentage-table gathers
+//   value 512: parsed-table gathers only for non-empty property ids (id 0 = "" parses to 0)
+//   value 2048: comparison-heavy build (product): CalcDiff windows dominate (realised lists are
 //           non-empty), so the bulk emission is not software-pipelined and the kernel
 //           targets DIFF_WAVES waves per SIMD; kdtn_epoch_run picks it when M > 0 and N > 0
-//   bit 12: (A/B) bulk loop: the next record's segment search before this record's gathers
-//   bit 15: (A/B) bulk emission stages the wave's 64 qdisc structs at once and stores them with
-//           16-B stores (about half the store instructions of two 32-struct halves of 8-B stores)
-//   bit 14: first bulk record's columns loaded before the gate / count / base phases (product;
+//   value 16384: first bulk record's columns loaded before the gate / count / base phases (product;
 //           A/B vs 515: 0.6164 / 0.6180 ms at 1M pods, 0.0849 / 0.0869 at 125k, 0.1563 / 0.1583 config 4)
-//   bit 16: bulk emission by LDS-DMA: each wave copies whole 64-record tiles of the link store
-//           (the 20 of 22 column units an entry reads, 1 KiB per global_load_lds_dwordx4) into its
-//           LDS slot and reads its record's columns there; the next tile's copy is issued behind
-//           this record's gathers
-constexpr int VAR_NT_LOAD = 1, VAR_NT_STORE = 2, VAR_NO_QSTORE = 4, VAR_NT_POD = 8, VAR_TRACE = 16,
-              VAR_SKIP_POD = 32, VAR_SKIP_PCT = 64, VAR_OCC5 = 128, VAR_OCC6 = 256,
-              VAR_MASK_EMPTY = 512, VAR_NO_PREFIX = 1024, VAR_DIFF = 2048, VAR_DECODE_FIRST = 4096, VAR_PREFETCH = 16384,
-              VAR_Q16 = 32768, VAR_GLDS = 65536,
-              VAR_PMAC_COLS = 131072,    // (internal to VAR_GLDS) the entry's peer_mac id is in RecCols
-              VAR_AB = 262144,           // CalcDiff window: old + positional new records in one load phase
+// Unused, never renumbered: 8, 128, 256, 1024, 4096, 32768, 65536, 131072, 262144, 4194304
+constexpr int VAR_NT_LOAD = 1, VAR_NT_STORE = 2, VAR_NO_QSTORE = 4, VAR_TRACE = 16,
+              VAR_SKIP_POD = 32, VAR_SKIP_PCT = 64,
+              VAR_MASK_EMPTY = 512, VAR_DIFF = 2048, VAR_PREFETCH = 16384,
               VAR_SKIP_KB1 = 524288,     // (profiling, wrong results) skip the local-MAC bitset gather
               VAR_SKIP_KB3 = 1048576,    // (profiling, wrong results) skip all three bitset gathers
-              VAR_HB = 2097152,          // CalcDiff window: both sides' key hashes first, one load round per old record
-              VAR_POD8 = 4194304;        // (profiling, wrong results) the pod-slot gather as an 8-B load from
-                                         // an 8-MB table: the footprint of a compact slot, timing only
-// VAR_GLDS: the tile column units an add entry reads, in LDS order: local_ip, local_mac (key 1, 2),
-// peer_ip, peer_mac, peer_pod (key 4..6), the 12 properties, gap, uid (2 units): every column of
-// the tile but local_intf and peer_intf. A delete reads units 0, 1 and the uid (at units 2, 3).
-constexpr int GL_UNITS = 20;
-KD_INLINE int gl_col(int u) { return u < 2 ? u + 1 : u + 2; }     // add tile: LDS unit -> tile column unit
-KD_INLINE int gl_col_del(int u) { return u < 2 ? u + 1 : u + 18; }   // delete tile (units 0..3)
+              VAR_HB = 2097152;          // CalcDiff window: both sides' key hashes first, one load round per old record
 constexpr int DIFF_WAVES = 5;
-constexpr int var_waves(int v) {
-    return (v & VAR_OCC6) ? 6 : (v & VAR_OCC5) ? 5 : (v & VAR_DIFF) ? DIFF_WAVES : (v & (VAR_PREFETCH | VAR_GLDS)) ? 4 : 1;
-}
+constexpr int var_waves(int v) { return (v & VAR_DIFF) ? DIFF_WAVES : (v & VAR_PREFETCH) ? 4 : 1; }
 constexpr int TRACE_WORDS = 8;   // entry, topologies loaded, counts done, bases known, end, hw ids,
                                   // CalcDiff window phase A done, phase B done (fast path)
 constexpr int DEFAULT_VARIANT = VAR_NT_LOAD | VAR_NT_STORE | VAR_MASK_EMPTY | VAR_PREFETCH;   // 16899
 // the comparison-heavy build kdtn_epoch_run launches when both link lists are non-empty; its
 // CalcDiff windows hash both sides' keys first (VAR_HB: 0.845 -> 0.671 ms on 5 config-3 churn
-// epochs, profiles/r06q_window_hb_cfg3.json; VAR_AB measured and not kept, r06d)
+// epochs, profiles/r06q_window_hb_cfg3.json; the merged-phase window, value 262144, measured and not kept, r06d)
 constexpr int DIFF_VARIANT = DEFAULT_VARIANT | VAR_DIFF | VAR_HB;   // 2116099
-// instantiations of the profiling build (DEFAULT_VARIANT is always instantiated): e.g. 547 / 579
-// / 611 skip the pod-slot / percentage / both gathers, 519 skips the qdisc stores, 531 the
-// trace build of the default
-#define KDTN_PROFILING_VARIANTS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(9) X(11) X(17) X(33) X(65) X(97) \
-    X(101) X(113) X(129) X(257) X(513) X(521) X(523) X(529) X(531) X(545) X(547) X(579) X(611) X(519) \
-    X(641) X(643) X(771) X(1025) X(1537) X(2579) X(4611) X(515) X(16915) X(16963) X(16931) X(16995) X(16903) X(49667) \
-    X(66051) X(65539) X(281091) X(264723) X(541187) X(1065475) X(18947) X(2099731) X(4211203)
+// instantiations of the profiling build (DEFAULT_VARIANT and DIFF_VARIANT are always
+// instantiated): e.g. 547 / 579 / 611 skip the pod-slot / percentage / both gathers, 519 skips
+// the qdisc stores, 531 the trace build of the default
+#define KDTN_PROFILING_VARIANTS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(17) X(33) X(65) X(97) \
+    X(101) X(113) X(513) X(529) X(531) X(545) X(547) X(579) X(611) X(519) \
+    X(2579) X(515) X(16915) X(16963) X(16931) X(16995) X(16903) \
+    X(541187) X(1065475) X(18947) X(2099731)
 
 struct DevTopos {
     const uint32_t* ns;
@@ -260,15 +226,9 @@ __global__ void k_place(DevTopos T, const uint32_t* wcount, const uint32_t* wbas
 constexpr int PLACE_SCAN_BLOCK = 1024, PLACE_PER = 8;    // k_place_scan: workgroups per thread per tile
 
 __global__ void k_special_clip(uint32_t* special, uint32_t k0);
-template <int SUB, bool X4, int NT>
 __global__ void k_kdict_flags(const uint8_t* bytes, const uint32_t* offs, uint32_t first, uint32_t n,
                               uint32_t* kbits, uint32_t kb_words, uint32_t* special);
-__global__ void k_kdict_flags_ws(const uint8_t* bytes, const uint32_t* offs, uint32_t first, uint32_t n,
-                                 uint32_t* kbits, uint32_t kb_words, uint32_t* special);
-__global__ void k_kdict_flags_pp(const uint8_t* bytes, const uint32_t* offs, uint32_t first, uint32_t n,
-                                 uint32_t* kbits, uint32_t kb_words, uint32_t* special);
-__global__ void k_kdict_flags_v1(const uint8_t* bytes, const uint32_t* offs, uint32_t first, uint32_t n,
-                                 uint32_t* kbits, uint32_t kb_words, uint32_t* special);
+// (profiling build only) floors of k_kdict_flags: the launch alone, the loads alone
 __global__ void k_kdict_null(const uint8_t* bytes, const uint32_t* offs, uint32_t first, uint32_t n,
                              uint32_t* kbits, uint32_t kb_words, uint32_t* special);
 __global__ void k_kdict_loadonly(const uint8_t* bytes, const uint32_t* offs, uint32_t first, uint32_t n,
@@ -276,22 +236,13 @@ __global__ void k_kdict_loadonly(const uint8_t* bytes, const uint32_t* offs, uin
 template <int WHICH>
 __global__ void k_pdict_only(const uint8_t* bytes, const uint32_t* offs, uint32_t first, uint32_t n, double tick,
                              uint32_t* ppct, uint2* pdur, uint2* prate, uint32_t* rate_err);
-enum : int { PD_DUR = 1, PD_PCT = 2, PD_RATE = 4, PD_RATE_GENERIC = 8 /* (A/B) no ASCII fast path */ };
-template <bool SPLIT>
+enum : int { PD_DUR = 1, PD_PCT = 2, PD_RATE = 4 };
 __global__ void k_pdict_parse(const uint8_t* bytes, const uint32_t* offs, uint32_t first, uint32_t n, double tick,
                               uint32_t* ppct, uint2* pdur, uint2* prate, uint32_t* rate_err);
 __global__ void k_pods_fill(DevTopos T, uint32_t slice, uint32_t rank_base, uint4* pods);
-__global__ void k_dict_parse(const uint8_t* kd_bytes, const uint32_t* kd_offs, uint32_t k0, uint32_t D, uint32_t* kbits,
-                             uint32_t kb_words, uint32_t* special, const uint8_t* pd_bytes, const uint32_t* pd_offs,
-                             uint32_t p0, uint32_t P, uint32_t nbp, double tick, uint32_t* ppct, uint2* pdur,
-                             uint2* prate, uint32_t* rate_err, uint32_t nbk_first);
-__global__ void k_dict_parse_w7(const uint8_t* kd_bytes, const uint32_t* kd_offs, uint32_t k0, uint32_t D,
-                                uint32_t* kbits, uint32_t kb_words, uint32_t* special, const uint8_t* pd_bytes,
-                                const uint32_t* pd_offs, uint32_t p0, uint32_t P, uint32_t nbp, double tick,
-                                uint32_t* ppct, uint2* pdur, uint2* prate, uint32_t* rate_err, uint32_t nbk_first);
 __global__ void k_epoch_begin(uint4* sync, uint32_t n16, uint32_t nbz, DevTopos T, uint32_t slice, uint32_t rank_base,
                               uint4* pods);
-template <int PER>
+constexpr int POD_PER = 4;   // pod rows per thread of k_pod_direct_scatter and k_pod_verify_prefix
 __global__ void k_pod_direct_scatter(const uint4* pods, uint32_t total, const uint32_t* phys_bits,
                                      const uint8_t* kd_bytes, const uint32_t* kd_offs, uint4* slots, uint32_t stamp,
                                      uint32_t nd, uint32_t nr, uint32_t gathered);
@@ -304,8 +255,6 @@ __global__ void k_pdict_verify(const uint4* pods, uint32_t total, uint4* slots, 
                                uint32_t* first_partial_inv, uint32_t nbv, uint32_t nbp, const uint8_t* pbytes,
                                const uint32_t* poffs, uint32_t p0, uint32_t np, uint32_t nbd, double tick,
                                uint32_t* ppct, uint2* pdur, uint2* prate, uint32_t* rate_err);
-__global__ void k_pod_direct_verify(const uint4* pods, uint32_t total, uint4* slots, uint32_t stamp,
-                                    unsigned long long* ovf, uint32_t mask, uint32_t nd);
 __global__ void k_vni_ht_build(const uint4* ents, uint32_t n, uint32_t* slots, uint32_t mask);
 __global__ void k_vni_fill(const uint4* ents, const uint32_t* slots, uint32_t nslots, uint4* out);
 __global__ void k_vni_pack(const uint32_t* node, const int32_t* vni, const uint32_t* net_ns,
@@ -702,7 +651,6 @@ __global__ void k_wire_write(WireIn w, DevLinks O, DevLinks N, WireWork wk, uint
 __global__ void k_qdisc_batch(DevLinks props, DevTables tb, uint2* out);
 constexpr int FP_BLOCK = 1024, FP_GRID = 256;       // k_full_prefix launch shape
 __global__ void k_full_prefix(DevTopos T, uint32_t* first_partial_inv);
-template <int PER>
 __global__ void k_pod_verify_prefix(const uint4* pods, uint32_t total, uint4* slots, uint32_t stamp,
                                     unsigned long long* ovf, uint32_t mask, uint32_t nd, DevTopos T,
                                     uint32_t* first_partial_inv, uint32_t nbv, uint32_t nr, uint32_t gathered);

@@ -62,11 +62,6 @@ template <typename T>
 KD_INLINE T ldg(const T* base, uint32_t idx) {
     return *reinterpret_cast<const T*>(reinterpret_cast<const uint8_t*>(base) + idx * (uint32_t)sizeof(T));
 }
-template <typename T>
-KD_INLINE T ldg_nt(const T* base, uint32_t idx) {
-    return __builtin_nontemporal_load(
-        reinterpret_cast<const T*>(reinterpret_cast<const uint8_t*>(base) + idx * (uint32_t)sizeof(T)));
-}
 
 // largest tt in [lo, hi) with off[tt] <= idx  (the segment containing idx)
 KD_INLINE int find_seg(const uint32_t* off, int lo, int hi, uint32_t idx) {
@@ -119,15 +114,9 @@ KD_INLINE uint32_t swar_eq(uint32_t x, uint32_t rep) {
 }
 // gather the 4 byte-high bits into a nibble (byte k → bit k): the products never overlap
 KD_INLINE uint32_t swar_nib(uint32_t m) { return (((m >> 7) * 0x204081u) >> 21) & 0xFu; }
-// 4 bytes of the string starting at byte q (q <= 19) of the 24-byte register image
-KD_INLINE uint32_t window4(const uint32_t* w, uint32_t q) {
-    const uint32_t i = q >> 2;
-    const uint32_t lo = i == 0 ? w[0] : i == 1 ? w[1] : i == 2 ? w[2] : i == 3 ? w[3] : w[4];
-    const uint32_t hi = i == 0 ? w[1] : i == 1 ? w[2] : i == 2 ? w[3] : i == 3 ? w[4] : w[5];
-    return __builtin_amdgcn_alignbyte(hi, lo, q & 3u);
-}
-// the same for q <= 19 without control flow: word pairs selected by the bits of q >> 2
-// (window4's nested selects compiled to branches and exec-mask updates per window)
+// 4 bytes of the string starting at byte q (q <= 19) of the 24-byte register image, without
+// control flow: word pairs selected by the bits of q >> 2 (nested selects on q >> 2 compiled
+// to branches and exec-mask updates per window)
 KD_INLINE uint32_t window4_bf(const uint32_t* w, uint32_t q) {
     const uint32_t i = q >> 2;
     const bool o = i & 1u, t = i & 2u, f = i & 4u;
@@ -168,46 +157,6 @@ KD_INLINE uint32_t octet_ok(uint32_t c, uint32_t n) {
     return (n >= 1u) & (n <= 3u) & ((n == 1u) | (d0 != 0u)) & ((n != 3u) | (v <= 255u));
 }
 
-// net.ParseCIDR validity from the register image of a string of <= 24 bytes
-// (common/veth.go:22). Decides every string without ':' whose prefix has <= 2 digits;
-// sets *slow for the rest (IPv6 candidates, long prefixes), which take cidr_ok().
-KD_INLINE bool cidr_swar(const uint32_t* w, uint32_t len, bool* slow) {
-    uint32_t D = 0, P = 0, S = 0, C = 0;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        D |= swar_nib(swar_digit(w[k])) << (4 * k);
-        P |= swar_nib(swar_eq(w[k], 0x2E2E2E2Eu)) << (4 * k);   // '.'
-        S |= swar_nib(swar_eq(w[k], 0x2F2F2F2Fu)) << (4 * k);   // '/'
-        C |= swar_nib(swar_eq(w[k], 0x3A3A3A3Au)) << (4 * k);   // ':'
-    }
-    const uint32_t L = (1u << len) - 1u;
-    D &= L;
-    P &= L;
-    S &= L;
-    C &= L;
-    const uint32_t s = __builtin_ctz(S | 0x1000000u);           // first '/' (24 if none)
-    const uint32_t m = len - s - 1u;                             // prefix digits
-    // generic parser only for IPv6 candidates (any IPv6 text has a colon) and for IPv4-looking
-    // strings (first byte a digit) with a prefix of 3+ digits; anything else cannot parse
-    // (ParseCIDR fails at once without a '/': MAC-shaped strings with ':' need no IPv6 parse)
-    *slow = (C != 0u && S != 0u) | ((D & 1u) != 0u && m > 2u && s < len);
-    const uint32_t sep = P | S;
-    uint32_t ok = ((D | sep) == L) & (__builtin_popcount(P) == 3) & (__builtin_popcount(S) == 1) &
-                  ((P >> s) == 0u) & ((sep & (sep << 1)) == 0u) & (D & 1u) & (s + 1u < len) & (s <= 15u);
-    const uint32_t p1 = __builtin_ctz(P | 0x1000000u);
-    const uint32_t P2 = P & (P - 1u);
-    const uint32_t p2 = __builtin_ctz(P2 | 0x1000000u);
-    const uint32_t p3 = __builtin_ctz((P2 & (P2 - 1u)) | 0x1000000u);
-    if (!ok) return false;                                       // positions below are in range
-    ok &= octet_ok(window4(w, 0), p1);
-    ok &= octet_ok(window4(w, p1 + 1u), p2 - p1 - 1u);
-    ok &= octet_ok(window4(w, p2 + 1u), p3 - p2 - 1u);
-    ok &= octet_ok(window4(w, p3 + 1u), s - p3 - 1u);
-    const uint32_t c = window4(w, s + 1u);                       // dtoi(prefix) <= 32
-    const uint32_t bits = m == 1u ? (c & 0xFFu) - '0' : ((c & 0xFFu) - '0') * 10u + (((c >> 8) & 0xFFu) - '0');
-    return ok && bits <= 32u;
-}
-
 // High-bit byte masks of two words → 8 position bits (bytes of lo at bits 0-3, of hi at 4-7):
 // lo >> 7 and hi >> 3 put the flags at bits 8j and 8j + 4, and one multiply by
 // 2^21 + 2^14 + 2^7 + 1 moves byte j's pair to bits 21 + j and 25 + j; the cross products land
@@ -215,10 +164,10 @@ KD_INLINE bool cidr_swar(const uint32_t* w, uint32_t len, bool* slow) {
 KD_INLINE uint32_t swar_nib8(uint32_t lo, uint32_t hi) {
     return __builtin_amdgcn_ubfe(((lo >> 7) | (hi >> 3)) * 0x204081u, 21, 8);
 }
-// net.ParseCIDR validity from the register image, same contract as cidr_swar (decides every
-// string of <= 24 bytes except the ones it routes to cidr_ok through *slow), with fewer VALU
-// operations — k_kdict_flags is VALU-issue bound (380 VALU instructions per wave at HEAD,
-// 4 cycles each on a SIMD16 = the kernel's time). No IPv4 CIDR with a prefix of <= 2 digits is
+// net.ParseCIDR validity from the register image of a string of <= 24 bytes
+// (common/veth.go:22). Decides every string without ':' whose prefix has <= 2 digits; sets
+// *slow for the rest (IPv6 candidates, long prefixes), which take cidr_ok(). Built for few VALU
+// operations: k_kdict_flags is VALU-issue bound. No IPv4 CIDR with a prefix of <= 2 digits is
 // longer than 18 bytes ("255.255.255.255/32"), so strings of <= 18 bytes are classified over
 // five words in byte space with one range test: every byte of a valid one is in '.'..'9'
 // (0x2E-0x39), the separators are the bytes below '0', and bit 0 tells '/' from '.'.
@@ -284,7 +233,6 @@ KD_INLINE bool cidr_swar2(const uint32_t* w, uint32_t len, bool* slow) {
 // the generic parsers (kdtn_parse.h) on global memory. Each wave packs its 64
 // predicate bits per set with a ballot (two u32 words per set, lanes 0 and 32).
 // Predicate bits of one key string from its register image (first 24 bytes in w[]).
-template <bool V1 = false>          // V1: the round-2 classifier (cidr_swar), A/B only
 KD_INLINE uint32_t kdict_bits(const uint8_t* bytes, uint32_t b, uint32_t len, const uint32_t* w, uint32_t i,
                               uint32_t* special) {
     uint32_t f = 0;
@@ -295,7 +243,7 @@ KD_INLINE uint32_t kdict_bits(const uint8_t* bytes, uint32_t b, uint32_t len, co
         f = (1u << KB_CIDR_BAD) | (1u << KB_MAC_BAD);
     } else if (len) {
         bool slow = true, cok = false;
-        if (len <= 24) cok = V1 ? cidr_swar(w, len, &slow) : cidr_swar2(w, len, &slow);
+        if (len <= 24) cok = cidr_swar2(w, len, &slow);
         if (slow) cok = cidr_ok(bytes + b, len);                       // common/veth.go:22
         if (!cok) f |= 1u << KB_CIDR_BAD;
         const uint32_t c2 = wbyte(w, 2), c4 = wbyte(w, 4);
@@ -369,178 +317,14 @@ KD_INLINE void kdict_block(const uint8_t* bytes, const uint32_t* offs, uint32_t 
     }
 }
 
-// SUB strings per thread (block covers SUB*BLOCK consecutive strings): every offset load
-// of the thread's strings is issued, then every string's 7 dwords, then the parses run —
-// the kernel is latency-bound, so a wave keeps SUB strings' round trips in flight at once.
 // Strings [first, n) (first a multiple of 64: every wave writes whole predicate words).
-// X4: the window comes from three 16-B aligned loads (48 bytes) instead of seven dwords.
-template <int SUB, bool X4, int NT>
-__global__ void __launch_bounds__(NT) k_kdict_flags(const uint8_t* bytes, const uint32_t* offs,
-                                                       uint32_t first, uint32_t n, uint32_t* kbits,
-                                                       uint32_t kb_words, uint32_t* special) {
-    const uint32_t i0 = first + blockIdx.x * NT * SUB + threadIdx.x;
-    uint32_t b[SUB], len[SUB];
-#pragma unroll
-    for (int s = 0; s < SUB; ++s) {
-        const uint32_t i = i0 + s * NT;
-        const uint32_t ic = i < n ? i : n;                 // offs[n] exists
-        b[s] = offs[ic];
-        len[s] = (i < n ? offs[ic + 1] : b[s]) - b[s];
-    }
-    uint32_t d[SUB][7];
-#pragma unroll
-    for (int s = 0; s < SUB; ++s) {
-        if constexpr (X4) {
-            const uint4* p = reinterpret_cast<const uint4*>(bytes + (b[s] & ~15u));    // arena has 64 B slack
-            const uint4 q0 = p[0], q1 = p[1], q2 = p[2];
-            const uint32_t D[12] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w};
-            const uint32_t o = (b[s] >> 2) & 3u;
-#pragma unroll
-            for (int k = 0; k < 7; ++k)
-                d[s][k] = o == 0 ? D[k] : o == 1 ? D[k + 1] : o == 2 ? D[k + 2] : D[k + 3];
-        } else {
-            kdict_window(bytes, b[s], len[s], d[s]);
-        }
-    }
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int s = 0; s < SUB; ++s) {
-        const uint32_t i = i0 + s * NT;
-        const uint32_t sh = (b[s] & 3u) * 8u;
-        uint32_t w[6];
-#pragma unroll
-        for (int k = 0; k < 6; ++k)
-            w[k] = sh ? (d[s][k] >> sh) | (d[s][k + 1] << (32u - sh)) : d[s][k];
-        const uint32_t f = i < n ? kdict_bits(bytes, b[s], len[s], w, i, special) : 0u;
-        const uint32_t w0 = (i - lane) >> 5;                   // first word of this wave
-#pragma unroll
-        for (int k = 0; k < KB_NSETS; ++k) {
-            const uint64_t m = __ballot((f >> k) & 1u);
-            if (w0 < kb_words && (lane == 0 || lane == 32))
-                kbits[(size_t)k * kb_words + w0 + (lane >> 5)] = lane ? (uint32_t)(m >> 32) : (uint32_t)m;
-        }
-    }
+__global__ void __launch_bounds__(BLOCK) k_kdict_flags(const uint8_t* bytes, const uint32_t* offs, uint32_t first,
+                                                       uint32_t n, uint32_t* kbits, uint32_t kb_words,
+                                                       uint32_t* special) {
+    kdict_block(bytes, offs, first + blockIdx.x * BLOCK, n, kbits, kb_words, special);
 }
-template __global__ void k_kdict_flags<1, false, BLOCK>(const uint8_t*, const uint32_t*, uint32_t, uint32_t, uint32_t*, uint32_t, uint32_t*);
 
 #if KDTN_PROFILING
-// (A/B, measured slower: 0.122 vs 0.112 ms at 1M pods, `KDTN_KD_SUB=16`) Wave-staged form:
-// the wave's 64 strings are contiguous in the arena, so the wave loads their
-// span once with 16-B coalesced loads into its LDS slot (one 128-B line per 8 lanes instead of
-// seven unaligned dword loads per lane touching ~10 lines each) and every lane reads its
-// seven window dwords from LDS. A span over KD_WS_BYTES (long strings) reads global memory.
-constexpr int KD_WS_BYTES = 2048;
-__global__ void __launch_bounds__(BLOCK) k_kdict_flags_ws(const uint8_t* bytes, const uint32_t* offs, uint32_t first,
-                                                          uint32_t n, uint32_t* kbits, uint32_t kb_words,
-                                                          uint32_t* special) {
-    __shared__ uint4 stage[BLOCK / 64][KD_WS_BYTES / 16];
-    const uint32_t i = first + blockIdx.x * BLOCK + threadIdx.x;
-    const int lane = threadIdx.x & 63;
-    uint4* st = stage[threadIdx.x >> 6];
-    const uint32_t ic = i < n ? i : n;                 // offs[n] exists
-    const uint32_t b = offs[ic];
-    const uint32_t len = (i < n ? offs[ic + 1] : b) - b;
-    const uint32_t base = (uint32_t)__shfl((int)b, 0, 64) & ~15u;
-    const uint32_t end = (uint32_t)__shfl((int)b, 63, 64) + 28u;     // the last lane's 7-dword window
-    const uint32_t n16 = (end - base + 15u) >> 4;
-    uint32_t d[7];
-    if (n16 <= (uint32_t)(KD_WS_BYTES / 16)) {                       // wave-uniform
-        const uint4* src = reinterpret_cast<const uint4*>(bytes + base);   // arena has 64 B slack
-        for (uint32_t w = lane; w < n16; w += 64) st[w] = src[w];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const uint32_t* lw = reinterpret_cast<const uint32_t*>(st) + (((b & ~3u) - base) >> 2);
-#pragma unroll
-        for (int k = 0; k < 7; ++k) d[k] = lw[k];
-    } else {
-        const uint32_t* p = reinterpret_cast<const uint32_t*>(bytes + (b & ~3u));
-#pragma unroll
-        for (int k = 0; k < 7; ++k) d[k] = p[k];
-    }
-    const uint32_t sh = (b & 3u) * 8u;
-    uint32_t w[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) w[k] = sh ? (d[k] >> sh) | (d[k + 1] << (32u - sh)) : d[k];
-    const uint32_t f = i < n ? kdict_bits(bytes, b, len, w, i, special) : 0u;
-    const uint32_t w0 = (i - lane) >> 5;                   // first word of this wave
-#pragma unroll
-    for (int k = 0; k < KB_NSETS; ++k) {
-        const uint64_t m = __ballot((f >> k) & 1u);
-        if (w0 < kb_words && (lane == 0 || lane == 32))
-            kbits[(size_t)k * kb_words + w0 + (lane >> 5)] = lane ? (uint32_t)(m >> 32) : (uint32_t)m;
-    }
-}
-// (A/B, KDTN_KD_SUB=32) Persistent waves, software-pipelined: each wave walks 64-string
-// chunks c = wave, wave + W, ... and issues chunk c + W's offset and window loads before it
-// parses chunk c, so a wave keeps one chunk's round trips in flight while it computes.
-__global__ void __launch_bounds__(BLOCK) k_kdict_flags_pp(const uint8_t* bytes, const uint32_t* offs, uint32_t first,
-                                                          uint32_t n, uint32_t* kbits, uint32_t kb_words,
-                                                          uint32_t* special) {
-    const int lane = threadIdx.x & 63;
-    const uint32_t W = gridDim.x * (BLOCK / 64);
-    uint32_t c = blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
-    const uint32_t nch = (n - first + 63) >> 6;
-    auto load = [&](uint32_t ch, uint32_t& b, uint32_t& len, uint32_t* d) {
-        const uint32_t i = first + ch * 64 + lane;
-        const uint32_t ic = i < n ? i : n;
-        b = offs[ic];
-        len = (i < n ? offs[ic + 1] : b) - b;
-        const uint32_t* p = reinterpret_cast<const uint32_t*>(bytes + (b & ~3u));
-#pragma unroll
-        for (int k = 0; k < 7; ++k) d[k] = p[k];
-    };
-    if (c >= nch) return;
-    uint32_t b, len, d[7];
-    load(c, b, len, d);
-    for (; c < nch; c += W) {
-        uint32_t nb = 0, nlen = 0, nd[7] = {0, 0, 0, 0, 0, 0, 0};
-        if (c + W < nch) load(c + W, nb, nlen, nd);
-        const uint32_t i = first + c * 64 + lane;
-        const uint32_t sh = (b & 3u) * 8u;
-        uint32_t w[6];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) w[k] = sh ? (d[k] >> sh) | (d[k + 1] << (32u - sh)) : d[k];
-        const uint32_t f = i < n ? kdict_bits(bytes, b, len, w, i, special) : 0u;
-        const uint32_t w0 = (i - lane) >> 5;
-#pragma unroll
-        for (int k = 0; k < KB_NSETS; ++k) {
-            const uint64_t m = __ballot((f >> k) & 1u);
-            if (w0 < kb_words && (lane == 0 || lane == 32))
-                kbits[(size_t)k * kb_words + w0 + (lane >> 5)] = lane ? (uint32_t)(m >> 32) : (uint32_t)m;
-        }
-        b = nb;
-        len = nlen;
-#pragma unroll
-        for (int k = 0; k < 7; ++k) d[k] = nd[k];
-    }
-}
-// (A/B, KDTN_KD_SUB=42) the product kernel with the round-2 classifier (cidr_swar)
-__global__ void __launch_bounds__(BLOCK) k_kdict_flags_v1(const uint8_t* bytes, const uint32_t* offs, uint32_t first,
-                                                          uint32_t n, uint32_t* kbits, uint32_t kb_words,
-                                                          uint32_t* special) {
-    const uint32_t i = first + blockIdx.x * BLOCK + threadIdx.x;
-    const int lane = threadIdx.x & 63;
-    const uint32_t ic = i < n ? i : n;
-    const uint32_t b = offs[ic];
-    const uint32_t len = (i < n ? offs[ic + 1] : b) - b;
-    const uint32_t* p = reinterpret_cast<const uint32_t*>(bytes + (b & ~3u));
-    uint32_t d[7];
-#pragma unroll
-    for (int k = 0; k < 7; ++k) d[k] = p[k];
-    const uint32_t sh = (b & 3u) * 8u;
-    uint32_t w[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) w[k] = sh ? (d[k] >> sh) | (d[k + 1] << (32u - sh)) : d[k];
-    const uint32_t f = i < n ? kdict_bits<true>(bytes, b, len, w, i, special) : 0u;
-    const uint32_t w0 = (i - lane) >> 5;
-#pragma unroll
-    for (int k = 0; k < KB_NSETS; ++k) {
-        const uint64_t m = __ballot((f >> k) & 1u);
-        if (w0 < kb_words && (lane == 0 || lane == 32))
-            kbits[(size_t)k * kb_words + w0 + (lane >> 5)] = lane ? (uint32_t)(m >> 32) : (uint32_t)m;
-    }
-}
 // (A/B, KDTN_KD_SUB=40) the launch floor: offsets only, one ballot store per wave and set
 __global__ void __launch_bounds__(BLOCK) k_kdict_null(const uint8_t* bytes, const uint32_t* offs, uint32_t first,
                                                       uint32_t n, uint32_t* kbits, uint32_t kb_words, uint32_t*) {
@@ -570,18 +354,11 @@ __global__ void __launch_bounds__(BLOCK) k_kdict_loadonly(const uint8_t* bytes, 
     if (w0 < kb_words && (lane == 0 || lane == 32))
         kbits[w0 + (lane >> 5)] = lane ? (uint32_t)(m >> 32) : (uint32_t)m;
 }
-template __global__ void k_kdict_flags<1, true, BLOCK>(const uint8_t*, const uint32_t*, uint32_t, uint32_t, uint32_t*, uint32_t, uint32_t*);
-template __global__ void k_kdict_flags<2, false, BLOCK>(const uint8_t*, const uint32_t*, uint32_t, uint32_t, uint32_t*, uint32_t, uint32_t*);
-template __global__ void k_kdict_flags<4, false, BLOCK>(
-    const uint8_t*, const uint32_t*, uint32_t, uint32_t, uint32_t*, uint32_t, uint32_t*);
-template __global__ void k_kdict_flags<1, false, 64>(
-    const uint8_t*, const uint32_t*, uint32_t, uint32_t, uint32_t*, uint32_t, uint32_t*);
-template __global__ void k_kdict_flags<1, false, 1024>(const uint8_t*, const uint32_t*, uint32_t, uint32_t, uint32_t*, uint32_t, uint32_t*);
 #endif
 
-// One property string's interpretations: WHICH = 7 all three, else one of PD_DUR / PD_PCT /
-// PD_RATE (the split launch gives each interpretation its own threads: more waves in flight
-// for a latency-bound parse, and each parse path alone needs fewer registers).
+// One property string's interpretations: WHICH = PD_DUR / PD_PCT / PD_RATE (each interpretation
+// has its own threads: more waves in flight for a latency-bound parse, and each parse path
+// alone needs fewer registers).
 template <int WHICH>
 KD_INLINE void pdict_parse_one(const uint8_t* s, uint32_t len, double tick, uint32_t* pct_out,
                                uint2* dur_out, uint2* rate_out, bool* rate_bad) {
@@ -596,7 +373,7 @@ KD_INLINE void pdict_parse_one(const uint8_t* s, uint32_t len, double tick, uint
     }
     if constexpr ((WHICH & PD_RATE) != 0) {
         uint64_t r = 0;
-        const bool rok = (WHICH & PD_RATE_GENERIC) ? parse_rate_generic(s, len, &r) : parse_rate(s, len, &r);
+        const bool rok = parse_rate(s, len, &r);
         *rate_out = rok ? make_uint2((uint32_t)r, (uint32_t)(r >> 32)) : make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
         *rate_bad = !rok;
     }
@@ -629,69 +406,16 @@ KD_INLINE void pdict_parse_block(const uint8_t* bytes, const uint32_t* offs, uin
 }
 
 // Strings [first, n) (first a multiple of 64: every wave writes whole rate_err words).
-// SPLIT: gridDim.y = 3, blockIdx.y picks the interpretation.
-template <bool SPLIT>
+// gridDim.y = 3, blockIdx.y picks the interpretation.
 __global__ void __launch_bounds__(BLOCK) k_pdict_parse(const uint8_t* bytes, const uint32_t* offs,
                                                        uint32_t first, uint32_t n, double tick, uint32_t* ppct,
                                                        uint2* pdur, uint2* prate, uint32_t* rate_err) {
     __shared__ uint4 buf[STAGE / 16];
     const uint32_t s0 = first + blockIdx.x * BLOCK;
-    if constexpr (SPLIT) {
-        if (blockIdx.y == 0) pdict_parse_block<PD_PCT>(bytes, offs, s0, n, tick, ppct, pdur, prate, rate_err, buf);
-        else if (blockIdx.y == 1) pdict_parse_block<PD_DUR>(bytes, offs, s0, n, tick, ppct, pdur, prate, rate_err, buf);
-        else pdict_parse_block<PD_RATE>(bytes, offs, s0, n, tick, ppct, pdur, prate, rate_err, buf);
-    } else {
-        pdict_parse_block<PD_DUR | PD_PCT | PD_RATE>(bytes, offs, s0, n, tick, ppct, pdur, prate, rate_err, buf);
-    }
+    if (blockIdx.y == 0) pdict_parse_block<PD_PCT>(bytes, offs, s0, n, tick, ppct, pdur, prate, rate_err, buf);
+    else if (blockIdx.y == 1) pdict_parse_block<PD_DUR>(bytes, offs, s0, n, tick, ppct, pdur, prate, rate_err, buf);
+    else pdict_parse_block<PD_RATE>(bytes, offs, s0, n, tick, ppct, pdur, prate, rate_err, buf);
 }
-// Both dictionaries' parses in one launch (independent work, one kernel boundary less per
-// epoch): blocks [0, 3 * nbp) parse property strings [p0, P), interpretation b / nbp (the
-// heavier blocks first), the rest classify key strings [k0, D) as k_kdict_flags does.
-KD_INLINE void dict_parse_block(const uint8_t* kd_bytes, const uint32_t* kd_offs, uint32_t k0, uint32_t D,
-                                 uint32_t* kbits, uint32_t kb_words, uint32_t* special, const uint8_t* pd_bytes,
-                                 const uint32_t* pd_offs, uint32_t p0, uint32_t P, uint32_t nbp, double tick,
-                                 uint32_t* ppct, uint2* pdur, uint2* prate, uint32_t* rate_err, uint32_t nbk,
-                                 uint4* buf) {
-    uint32_t b = blockIdx.x;
-    if (nbk) {                              // (key-string blocks first)
-        if (b < nbk) {
-            kdict_block(kd_bytes, kd_offs, k0 + b * BLOCK, D, kbits, kb_words, special);
-            return;
-        }
-        b -= nbk;
-    } else if (b >= 3 * nbp) {
-        kdict_block(kd_bytes, kd_offs, k0 + (b - 3 * nbp) * BLOCK, D, kbits, kb_words, special);
-        return;
-    }
-    const uint32_t y = b / nbp, s0 = p0 + (b - y * nbp) * BLOCK;
-    if (y == 0) pdict_parse_block<PD_PCT>(pd_bytes, pd_offs, s0, P, tick, ppct, pdur, prate, rate_err, buf);
-    else if (y == 1) pdict_parse_block<PD_DUR>(pd_bytes, pd_offs, s0, P, tick, ppct, pdur, prate, rate_err, buf);
-    else pdict_parse_block<PD_RATE>(pd_bytes, pd_offs, s0, P, tick, ppct, pdur, prate, rate_err, buf);
-}
-__global__ void __launch_bounds__(BLOCK) k_dict_parse(const uint8_t* kd_bytes, const uint32_t* kd_offs, uint32_t k0,
-                                                      uint32_t D, uint32_t* kbits, uint32_t kb_words,
-                                                      uint32_t* special, const uint8_t* pd_bytes,
-                                                      const uint32_t* pd_offs, uint32_t p0, uint32_t P, uint32_t nbp,
-                                                      double tick, uint32_t* ppct, uint2* pdur, uint2* prate,
-                                                      uint32_t* rate_err, uint32_t nbk) {
-    __shared__ uint4 buf[STAGE / 16];
-    dict_parse_block(kd_bytes, kd_offs, k0, D, kbits, kb_words, special, pd_bytes, pd_offs, p0, P, nbp, tick, ppct,
-                     pdur, prate, rate_err, nbk, buf);
-}
-#if KDTN_PROFILING
-// (A/B) the same held to the SGPR budget of 7 waves per SIMD (k_kdict_flags alone runs at 7;
-// the fused kernel's 112 SGPRs allow 6)
-__global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(7, 8)))
-k_dict_parse_w7(const uint8_t* kd_bytes, const uint32_t* kd_offs, uint32_t k0, uint32_t D, uint32_t* kbits,
-                uint32_t kb_words, uint32_t* special, const uint8_t* pd_bytes, const uint32_t* pd_offs, uint32_t p0,
-                uint32_t P, uint32_t nbp, double tick, uint32_t* ppct, uint2* pdur, uint2* prate, uint32_t* rate_err,
-                uint32_t nbk) {
-    __shared__ uint4 buf[STAGE / 16];
-    dict_parse_block(kd_bytes, kd_offs, k0, D, kbits, kb_words, special, pd_bytes, pd_offs, p0, P, nbp, tick, ppct,
-                     pdur, prate, rate_err, nbk, buf);
-}
-#endif
-
 #if KDTN_PROFILING
 // (profiling) one interpretation alone: WHICH = PD_DUR / PD_PCT / PD_RATE
 template <int WHICH>
@@ -707,13 +431,7 @@ template __global__ void k_pdict_only<PD_PCT>(const uint8_t*, const uint32_t*, u
                                               uint2*, uint2*, uint32_t*);
 template __global__ void k_pdict_only<PD_RATE>(const uint8_t*, const uint32_t*, uint32_t, uint32_t, double, uint32_t*,
                                                uint2*, uint2*, uint32_t*);
-template __global__ void k_pdict_only<PD_RATE | PD_RATE_GENERIC>(const uint8_t*, const uint32_t*, uint32_t, uint32_t,
-                                                                 double, uint32_t*, uint2*, uint2*, uint32_t*);
 #endif
-template __global__ void k_pdict_parse<false>(const uint8_t*, const uint32_t*, uint32_t, uint32_t, double, uint32_t*,
-                                              uint2*, uint2*, uint32_t*);
-template __global__ void k_pdict_parse<true>(const uint8_t*, const uint32_t*, uint32_t, uint32_t, double, uint32_t*,
-                                             uint2*, uint2*, uint32_t*);
 
 // ======================================================================================
 // pod-status table + lookup tables
@@ -814,24 +532,23 @@ KD_INLINE uint32_t name_physical(const uint8_t* kd_bytes, const uint32_t* kd_off
 }
 
 // phys_bits: the KB_PHYSICAL bitset of a finished key-string parse, or null (the PHYSICAL bit
-// from the name's bytes: the lookup build beside the parses, A/B)
-template <int PER>
+// from the name's bytes)
 __global__ void __launch_bounds__(BLOCK) k_pod_direct_scatter(const uint4* pods, uint32_t total,
                                                               const uint32_t* phys_bits, const uint8_t* kd_bytes,
                                                               const uint32_t* kd_offs, uint4* slots, uint32_t stamp,
                                                               uint32_t nd, uint32_t nr, uint32_t gathered) {
-    // PER rows per thread, every row load issued before the first slot store (latency-bound)
-    const uint32_t t0 = blockIdx.x * BLOCK * PER + threadIdx.x;
-    uint32_t g[PER];
-    uint4 e[PER];
+    // POD_PER rows per thread, every row load issued before the first slot store (latency-bound)
+    const uint32_t t0 = blockIdx.x * BLOCK * POD_PER + threadIdx.x;
+    uint32_t g[POD_PER];
+    uint4 e[POD_PER];
 #pragma unroll
-    for (int q = 0; q < PER; ++q) {
+    for (int q = 0; q < POD_PER; ++q) {
         const uint32_t t = t0 + q * BLOCK;
         g[q] = t < total ? pod_order(t, gathered, nr) : 0u;
         e[q] = t < total ? pods[g[q]] : make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);
     }
 #pragma unroll
-    for (int q = 0; q < PER; ++q) {
+    for (int q = 0; q < POD_PER; ++q) {
         if (e[q].x == 0xFFFFFFFFu || e[q].y >= nd) continue;   // padding row / name outside this dictionary
         const uint32_t y = e[q].y;
         const uint32_t phys = phys_bits ? (phys_bits[y >> 5] >> (y & 31)) & 1u : name_physical(kd_bytes, kd_offs, y);
@@ -839,14 +556,6 @@ __global__ void __launch_bounds__(BLOCK) k_pod_direct_scatter(const uint4* pods,
                               e[q].z | ((e[q].w & 0x7FFFFFFFu) == 0 ? 0x80000000u : 0u), stamp << 1);
     }
 }
-template __global__ void k_pod_direct_scatter<1>(const uint4*, uint32_t, const uint32_t*, const uint8_t*, const uint32_t*,
-                                                 uint4*, uint32_t, uint32_t, uint32_t, uint32_t);
-template __global__ void k_pod_direct_scatter<4>(const uint4*, uint32_t, const uint32_t*, const uint8_t*, const uint32_t*,
-                                                 uint4*, uint32_t, uint32_t, uint32_t, uint32_t);
-#if KDTN_PROFILING
-template __global__ void k_pod_direct_scatter<2>(const uint4*, uint32_t, const uint32_t*, const uint8_t*, const uint32_t*,
-                                                 uint4*, uint32_t, uint32_t, uint32_t, uint32_t);
-#endif
 
 // Pods whose name slot was won by another pod: mark the name `multi` and put both pods
 // into the overflow table (duplicates are rare; the table then answers every lookup of
@@ -862,12 +571,6 @@ KD_INLINE void pod_verify_one(const uint4* pods, uint32_t total, uint4* slots, u
     reinterpret_cast<uint32_t*>(slots + e.y)[3] = (stamp << 1) | 1u;
     ovf_insert(pods, g, e.x, e.y, ovf, mask, stamp);
     ovf_insert(pods, owner, pods[owner].x, e.y, ovf, mask, stamp);
-}
-
-__global__ void __launch_bounds__(BLOCK) k_pod_direct_verify(const uint4* pods, uint32_t total, uint4* slots,
-                                                             uint32_t stamp, unsigned long long* ovf, uint32_t mask,
-                                                             uint32_t nd) {
-    pod_verify_one(pods, total, slots, stamp, ovf, mask, nd, blockIdx.x * BLOCK + threadIdx.x);
 }
 
 __global__ void __launch_bounds__(BLOCK) k_vni_pack(const uint32_t* node, const int32_t* vni,
@@ -909,15 +612,7 @@ __global__ void __launch_bounds__(BLOCK) k_vni_ht_build(const uint4* ents, uint3
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-template <bool NT>
-KD_INLINE uint4 pod_slot(const DevTables& tb, uint32_t name) {
-    if constexpr (NT) {           // little reuse: keep L2 for the parsed tables
-        const u32x4 v = ldg_nt(reinterpret_cast<const u32x4*>(tb.pod_direct), name);
-        return make_uint4(v.x, v.y, v.z, v.w);
-    } else {
-        return ldg(tb.pod_direct, name);
-    }
-}
+KD_INLINE uint4 pod_slot(const DevTables& tb, uint32_t name) { return ldg(tb.pod_direct, name); }
 // Resolve a lookup of (ns, name) whose direct slot already read as w.
 // Returns {g | POD_SPEC_NIL | POD_PHYSICAL, src_ip | netns_empty<<31}; x = 0xFFFFFFFF on a miss.
 KD_INLINE uint2 pod_resolve(const DevTables& tb, uint32_t ns, uint32_t name, uint4 w) {
@@ -960,7 +655,6 @@ KD_INLINE uint32_t vni_lookup(const DevTables& tb, uint32_t node, int32_t vni) {
 // Columns of one link record that the outputs need, loaded together (one round trip).
 struct RecCols {
     uint32_t lip, lmac, pp, pip;      // local_ip, local_mac, peer_pod, peer_ip (kdict ids)
-    uint32_t pmac;                    // peer_mac (VAR_GLDS bulk emission only: VAR_PMAC_COLS)
     uint32_t prop[KDTN_NPROP];        // pdict ids
     uint32_t gap;
     int64_t uid;
@@ -1225,12 +919,7 @@ KD_INLINE void add_gather(const RecCols& c, const TopoCtx& tc, const DevTables& 
         else g.kb_mac = ldg(tb.kbits + (size_t)KB_MAC_BAD * tb.kb_words, c.lmac >> 5);
         g.kb_pip = ldg(tb.kbits + (size_t)KB_CIDR_BAD * tb.kb_words, c.pip >> 5);    // peer end (same / cross node)
     }
-    if constexpr ((V & VAR_POD8) != 0) {              // profiling only: 8 B from the table's first half
-        const u32x2 w = ldg(reinterpret_cast<const u32x2*>(tb.pod_direct), c.pp);
-        g.slot = make_uint4(w.x, w.y, 0u, 0u);
-    } else if constexpr ((V & VAR_SKIP_POD) == 0) {
-        g.slot = pod_slot<(V & VAR_NT_POD) != 0>(tb, c.pp);
-    }
+    if constexpr ((V & VAR_SKIP_POD) == 0) g.slot = pod_slot(tb, c.pp);
 }
 
 template <int V>
@@ -1251,10 +940,6 @@ KD_INLINE uint4 add_calc(const RecCols& c, const AddGath& g, const DevLinks& N, 
         const bool lh = c.pp == tb.special[SPECIAL_LOCALHOST];
         uint2 p = make_uint2(0xFFFFFFFFu, 0u);
         if constexpr ((V & VAR_SKIP_POD) != 0) p = make_uint2(c.pp & POD_INDEX, g.lns);   // profiling only
-        else if constexpr ((V & VAR_POD8) != 0) {                                          // profiling only
-            asm volatile("" ::"v"(g.slot.x), "v"(g.slot.y));
-            p = make_uint2(c.pp & POD_INDEX, g.lns);
-        }
         else if (!lh) p = pod_resolve(tb, g.lns, c.pp, g.slot);
         const bool miss = p.x == 0xFFFFFFFFu;
         if (lh) {
@@ -1276,7 +961,7 @@ KD_INLINE uint4 add_calc(const RecCols& c, const AddGath& g, const DevLinks& N, 
             } else if (p_src == tc.src) {
                 kind = KDTN_KIND_SAME_NODE;                                               // :399-418
                 err = pip_bad ? (uint32_t)KDTN_E_PEER_VETH_CIDR                         // MakeVeth(peer) :402
-                    : kbit(tb, KB_MAC_BAD, (V & VAR_PMAC_COLS) ? c.pmac : N.key_s<NTL>(KDTN_K_PEER_MAC, j))
+                    : kbit(tb, KB_MAC_BAD, N.key_s<NTL>(KDTN_K_PEER_MAC, j))
                         ? (uint32_t)KDTN_E_PEER_VETH_MAC : 0u;
             } else {
                 kind = KDTN_KIND_CROSS_NODE;                                              // :419-453
@@ -1361,45 +1046,6 @@ __device__ __forceinline__ void wave_store_qdisc(uint2* outq, bool active, uint3
     }
 }
 
-// (VAR_Q16) the wave's 64 structs staged at once and stored as 16-B words: the destination
-// range starts 8-B aligned, so at most one leading and one trailing 8-B word go alone
-template <int V>
-__device__ __forceinline__ void wave_store_qdisc16(uint2* outq, bool active, uint32_t e, const uint32_t* q,
-                                                   uint2* stage) {
-    const uint64_t m = __ballot(active);
-    if (m == 0) return;
-    const int lane = threadIdx.x & 63;
-    const uint32_t p0 = __shfl(e, __ffsll((long long)m) - 1, 64);
-    const uint32_t rank = __popcll(m & lanemask_lt()), cnt = __popcll(m);
-    if (active) {
-        uint2* slot = stage + rank * 9;
-#pragma unroll
-        for (int w = 0; w < 9; ++w) slot[w] = make_uint2(q[2 * w], q[2 * w + 1]);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const size_t base = (size_t)p0 * 9;
-    uint2* dst = outq + base;
-    const uint32_t nq = cnt * 9, head = (uint32_t)(base & 1u), n16 = (nq - head) >> 1;
-    if (head && lane == 0) store_q8<V>(dst, stage[0]);
-    u32x4* d16 = reinterpret_cast<u32x4*>(dst + head);
-    for (uint32_t k = lane; k < n16; k += 64) {
-        const uint2 a = stage[head + 2 * k], b = stage[head + 2 * k + 1];
-        u32x4 v;
-        v.x = a.x;
-        v.y = a.y;
-        v.z = b.x;
-        v.w = b.y;
-        if constexpr ((V & VAR_NT_STORE) != 0) __builtin_nontemporal_store(v, d16 + k);
-        else d16[k] = v;
-    }
-    if (((nq - head) & 1u) && lane == 0) store_q8<V>(dst + nq - 1, stage[nq - 1]);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // ======================================================================================
 // k_reconcile: one workgroup = TPW consecutive topologies (dynamic ticket order).
 // ======================================================================================
@@ -1417,23 +1063,15 @@ struct RecShared {
     uint32_t ticket;
     uint32_t any_cmp;
     uint32_t n_dense;
-    union {
-        struct {                  // comparison windows (gate + CalcDiff, fast-path emission)
-            uint16_t rank[CAP];  // entry position within the workgroup's list
-            uint16_t dense[CAP]; // fast path: the flagged records, in record order
-            uint16_t tgt[CAP];   // upd target, relative to the workgroup's first desired record
-            uint8_t flag[CAP];
-            uint8_t lt[CAP];
-            union {               // CalcDiff hashes, then (emission) per-wave qdisc staging
-                uint32_t hash[CAP];
-                uint2 stage[BLOCK / 64][32 * 9];
-            };
-        };
-        struct {                  // (VAR_GLDS, profiling build) bulk emission: one link tile per wave
-            uint32_t tiles[BLOCK / 64][KDTN_PROFILING ? GL_UNITS * TILE_RECS : 1];
-            uint2 bstage[BLOCK / 64][32 * 9];
-        };
-        uint2 stage64[BLOCK / 64][64 * 9];   // (VAR_Q16) bulk emission: a wave's 64 qdisc structs
+    // comparison windows (gate + CalcDiff, fast-path emission), 8-B aligned like the staging words
+    alignas(8) uint16_t rank[CAP];  // entry position within the workgroup's list
+    uint16_t dense[CAP]; // fast path: the flagged records, in record order
+    uint16_t tgt[CAP];   // upd target, relative to the workgroup's first desired record
+    uint8_t flag[CAP];
+    uint8_t lt[CAP];
+    union {               // CalcDiff hashes, then (emission) per-wave qdisc staging
+        uint32_t hash[CAP];
+        uint2 stage[BLOCK / 64][32 * 9];
     };
 };
 
@@ -1602,110 +1240,6 @@ __device__ __forceinline__ void diff_window_tail(RecShared& s, int tb, int te, c
         if (f & RF_ADD) atomicAdd(&s.tcnt[2][tt], 1u);
     }
     __syncthreads();
-}
-
-// (VAR_AB) the LDS window with its first two phases merged: every old record is loaded with
-// the new record at its position in ONE round trip (both keys and properties), both key hashes
-// go to LDS and the positional key / DeepEqual bits to the old record's flag byte; new records
-// past their topology's old count hash their own key. The scan phase then reads only LDS,
-// loading keys (and properties on a key match) for a hash hit off the positional record.
-// Saves the new records' separate key pass (a round trip and 36 B per new record).
-template <bool TR>
-__device__ void diff_window_ab(RecShared& s, int tb, int te, const DevLinks& O, const DevLinks& N, uint32_t* hsh,
-                               uint8_t* flg, uint8_t* lt, uint16_t* tgt16, unsigned long long* tr = nullptr) {
-    const uint32_t wo0 = s.ooff[tb], wo1 = s.ooff[te];
-    const uint32_t wn0 = s.noff[tb], wn1 = s.noff[te];
-    const uint32_t no = wo1 - wo0, nn = wn1 - wn0, tot = no + nn;
-    const int tid = threadIdx.x;
-    constexpr uint8_t POS_KEY = 1, POS_EQ = 2;
-
-    // A. loads and hashes
-    for (uint32_t r = tid; r < tot; r += BLOCK) {
-        const bool old = r < no;
-        const uint32_t idx = old ? wo0 + r : wn0 + (r - no);
-        const int tt = find_seg(old ? s.ooff : s.noff, tb, te, idx);
-        lt[r] = (uint8_t)tt;
-        uint8_t f = 0;
-        if (need_cmp(s, tt)) {
-            const uint32_t os_ = s.ooff[tt], ns_ = s.noff[tt], ne_ = s.noff[tt + 1];
-            const uint32_t ko = s.ooff[tt + 1] - os_;
-            if (old) {
-                const uint32_t jp = ns_ + (idx - os_);
-                const bool have_p = jp < ne_;
-                uint32_t ki[KEYW], pi[PROPW], kj[KEYW], pj[PROPW];
-                load_key(O, idx, ki);
-                load_props(O, idx, pi);
-                if (have_p) {
-                    load_key(N, jp, kj);
-                    load_props(N, jp, pj);
-                }
-                hsh[r] = key_hash_w(ki);
-                if (have_p) hsh[no + (jp - wn0)] = key_hash_w(kj);
-                const bool pos_key = have_p && words_eq<KEYW>(ki, kj);
-                const bool pos_eq = pos_key && words_eq<PROPW>(pi, pj);
-                f = (pos_key ? POS_KEY : 0) | (pos_eq ? POS_EQ : 0);
-                if (ko == ne_ - ns_ && !pos_eq) s.dirty[tt] = 1;
-            } else if (idx - ns_ >= ko) {                    // no old record at its position
-                uint32_t k[KEYW];
-                load_key(N, idx, k);
-                hsh[r] = key_hash_w(k);
-            }
-        }
-        flg[r] = f;
-    }
-    __syncthreads();
-    if constexpr (TR) {
-        if (tid == 0) tr[6] = __builtin_amdgcn_s_memrealtime();
-    }
-
-    // B. old side: first key-equal new record (CalcDiff :289-303), from the LDS hashes
-    for (uint32_t r = tid; r < no; r += BLOCK) {
-        const int tt = lt[r];
-        uint8_t f = RF_DEL;
-        if (need_cmp(s, tt)) {
-            const uint32_t i = wo0 + r;
-            const uint32_t os_ = s.ooff[tt], ns_ = s.noff[tt], ne_ = s.noff[tt + 1];
-            const uint32_t jp = ns_ + (i - os_);
-            const uint8_t pb = flg[r];
-            const bool pos_key = pb & POS_KEY, pos_eq = pb & POS_EQ;
-            const uint32_t h = hsh[r];
-            uint32_t first = 0xFFFFFFFFu;
-            bool same_props = false;
-            const uint32_t jend = pos_key ? jp : ne_;        // before jp: an earlier duplicate only
-            for (uint32_t j = ns_; j < jend; ++j) {
-                if (j == jp || hsh[no + (j - wn0)] != h) continue;
-                uint32_t ki[KEYW], kx[KEYW], pi[PROPW], px[PROPW];   // one round trip per candidate
-                load_key(O, i, ki);
-                load_key(N, j, kx);
-                load_props(O, i, pi);
-                load_props(N, j, px);
-                if (words_eq<KEYW>(ki, kx)) {
-                    first = j;
-                    same_props = words_eq<PROPW>(pi, px);
-                    break;
-                }
-            }
-            if (first == 0xFFFFFFFFu && pos_key) {
-                first = jp;
-                same_props = pos_eq;
-            }
-            if (first != 0xFFFFFFFFu) {
-                flg[no + (first - wn0)] = RF_MATCHED;
-                if (!same_props) {
-                    f = RF_UPD;
-                    tgt16[r] = (uint16_t)(first - wn0);
-                } else {
-                    f = 0;
-                }
-            }
-        }
-        flg[r] = f;
-    }
-    __syncthreads();
-    if constexpr (TR) {
-        if (tid == 0) tr[7] = __builtin_amdgcn_s_memrealtime();
-    }
-    diff_window_tail(s, tb, te, N, hsh, flg, lt, no, nn, tot, wn0);
 }
 
 // (VAR_HB) the LDS window with both sides' key hashes in the first phase (each record's 9 key
@@ -1953,49 +1487,36 @@ __global__ void __launch_bounds__(FP_BLOCK) k_full_prefix(DevTopos T, uint32_t* 
     full_prefix_blocks<FP_BLOCK>(T, first_partial_inv, blockIdx.x, gridDim.x, &bmin);
 }
 
-// k_pod_direct_verify and k_full_prefix in one launch (independent work; one kernel boundary
+// The pod-slot verify and k_full_prefix in one launch (independent work; one kernel boundary
 // less per epoch): blocks [0, nbv) verify pods, the rest scan topologies.
-template <int PER>
 __global__ void __launch_bounds__(BLOCK) k_pod_verify_prefix(const uint4* pods, uint32_t total, uint4* slots,
                                                              uint32_t stamp, unsigned long long* ovf, uint32_t mask,
                                                              uint32_t nd, DevTopos T, uint32_t* first_partial_inv,
                                                              uint32_t nbv, uint32_t nr, uint32_t gathered) {
     __shared__ uint32_t bmin;
     if (blockIdx.x < nbv) {
-        if constexpr (PER == 1) {
-            const uint32_t t = blockIdx.x * BLOCK + threadIdx.x;
-            if (t < total) pod_verify_one(pods, total, slots, stamp, ovf, mask, nd, pod_order(t, gathered, nr));
-        } else {                                  // PER rows per thread: row loads, then slot owner words
-            const uint32_t t0 = blockIdx.x * BLOCK * PER + threadIdx.x;
-            uint32_t g[PER], own[PER];
-            uint4 e[PER];
+        // POD_PER rows per thread: row loads, then slot owner words
+        const uint32_t t0 = blockIdx.x * BLOCK * POD_PER + threadIdx.x;
+        uint32_t g[POD_PER], own[POD_PER];
+        uint4 e[POD_PER];
 #pragma unroll
-            for (int q = 0; q < PER; ++q) {
-                const uint32_t t = t0 + q * BLOCK;
-                g[q] = t < total ? pod_order(t, gathered, nr) : 0u;
-                e[q] = t < total ? pods[g[q]] : make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);
-            }
-#pragma unroll
-            for (int q = 0; q < PER; ++q)
-                own[q] = (e[q].x == 0xFFFFFFFFu || e[q].y >= nd) ? g[q] << 2
-                         : reinterpret_cast<const uint32_t*>(slots + e[q].y)[1];
-#pragma unroll
-            for (int q = 0; q < PER; ++q)
-                if ((own[q] >> 2) != g[q]) pod_verify_one(pods, total, slots, stamp, ovf, mask, nd, g[q]);
+        for (int q = 0; q < POD_PER; ++q) {
+            const uint32_t t = t0 + q * BLOCK;
+            g[q] = t < total ? pod_order(t, gathered, nr) : 0u;
+            e[q] = t < total ? pods[g[q]] : make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);
         }
+#pragma unroll
+        for (int q = 0; q < POD_PER; ++q)
+            own[q] = (e[q].x == 0xFFFFFFFFu || e[q].y >= nd) ? g[q] << 2
+                     : reinterpret_cast<const uint32_t*>(slots + e[q].y)[1];
+#pragma unroll
+        for (int q = 0; q < POD_PER; ++q)
+            if ((own[q] >> 2) != g[q]) pod_verify_one(pods, total, slots, stamp, ovf, mask, nd, g[q]);
         return;
     }
     full_prefix_blocks<BLOCK>(T, first_partial_inv, blockIdx.x - nbv, gridDim.x - nbv, &bmin);
 }
 
-template __global__ void k_pod_verify_prefix<1>(const uint4*, uint32_t, uint4*, uint32_t, unsigned long long*, uint32_t,
-                                                uint32_t, DevTopos, uint32_t*, uint32_t, uint32_t, uint32_t);
-template __global__ void k_pod_verify_prefix<4>(const uint4*, uint32_t, uint4*, uint32_t, unsigned long long*, uint32_t,
-                                                uint32_t, DevTopos, uint32_t*, uint32_t, uint32_t, uint32_t);
-#if KDTN_PROFILING
-template __global__ void k_pod_verify_prefix<2>(const uint4*, uint32_t, uint4*, uint32_t, unsigned long long*, uint32_t,
-                                                uint32_t, DevTopos, uint32_t*, uint32_t, uint32_t, uint32_t);
-#endif
 // ---- fused epoch front (one local rank: no exchange) -------------------------------------
 // Two launches instead of five when the key-string parse is short (kdtn_epoch_run's rule):
 // the pod tables' memory-bound work shares launches with the dictionary parses. With a long
@@ -2073,79 +1594,6 @@ KD_INLINE void trace_mark(const RecWork& wk, uint32_t wg, int k, unsigned long l
     }
 }
 
-// ---- VAR_GLDS: bulk emission from LDS-DMA'd link tiles ----------------------------------
-// The records [rlo, rhi) of a bulk chunk (old part [0, no) then new part) as whole 64-record
-// tiles of the two link stores: tile g of the list is old tile to0 + g (g < nto), else new tile
-// tn0 + g - nto. A wave takes tiles wave, wave + 4, ...; lane l handles record 64 t + l.
-struct GlPlan {
-    uint32_t oa, ob, na, nb;          // old / new record ranges
-    uint32_t to0, nto, tn0, nt;       // first tiles, old tile count, all tiles
-};
-KD_INLINE GlPlan gl_plan(uint32_t rlo, uint32_t rhi, uint32_t no, uint32_t o0, uint32_t n0) {
-    GlPlan p;
-    p.oa = o0 + min(rlo, no);
-    p.ob = o0 + min(rhi, no);
-    p.na = n0 + (max(rlo, no) - no);
-    p.nb = n0 + (max(rhi, no) - no);
-    p.to0 = p.oa >> 6;
-    p.nto = p.ob > p.oa ? ((p.ob - 1) >> 6) - p.to0 + 1 : 0u;
-    p.tn0 = p.na >> 6;
-    p.nt = p.nto + (p.nb > p.na ? ((p.nb - 1) >> 6) - p.tn0 + 1 : 0u);
-    return p;
-}
-
-// One 16-B piece per lane into this wave's LDS slot: lane l of the instruction writes bytes
-// [16 l, 16 l + 16) after `dst` (wave-uniform); the source address is the lane's own.
-template <bool NT>
-KD_INLINE void glds16(const void* src, uint32_t* dst) {
-    __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)dst, 16, 0, NT ? 2 : 0);
-}
-
-// Copy tile g of the plan into `slot`: an add tile as GL_UNITS column units (5 instructions of
-// 64 pieces), a delete tile as 4 (local_ip, local_mac, uid; one instruction). A piece whose
-// records all lie outside the plan's range (the chunk's edge tiles) is not copied.
-template <bool NT>
-KD_INLINE void gl_issue(const GlPlan& p, uint32_t g, const DevLinks& O, const DevLinks& N, uint32_t* slot,
-                        int lane) {
-    if (g >= p.nt) return;
-    const bool old = g < p.nto;
-    const uint32_t t = old ? p.to0 + g : p.tn0 + (g - p.nto);
-    const uint32_t lo = old ? p.oa : p.na, hi = old ? p.ob : p.nb, t64 = t * 64u;
-    const uint32_t rlo = lo > t64 ? lo - t64 : 0u, rhi = min(hi - t64, 64u);
-    const uint8_t* tile = reinterpret_cast<const uint8_t*>((old ? O.base : N.base) + (size_t)t * TILE_WORDS);
-    const int k = lane & 15;
-    if (old) {
-        const int u = lane >> 4;
-        const uint32_t r0 = u < 2 ? k * 4 : (u - 2) * 32 + k * 2, r1 = r0 + (u < 2 ? 4 : 2);
-        if (r0 < rhi && r1 > rlo) glds16<NT>(tile + gl_col_del(u) * 256 + k * 16, slot);
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < GL_UNITS / 4; ++i) {
-        const int u = i * 4 + (lane >> 4);
-        const uint32_t r0 = u < 18 ? k * 4 : (u - 18) * 32 + k * 2, r1 = r0 + (u < 18 ? 4 : 2);
-        if (r0 < rhi && r1 > rlo) glds16<NT>(tile + gl_col(u) * 256 + k * 16, slot + i * 256);
-    }
-}
-
-// This lane's record columns from the wave's tile slot
-KD_INLINE void gl_cols(const uint32_t* slot, int lane, bool old, RecCols& c) {
-    c.lip = slot[lane];
-    c.lmac = slot[64 + lane];
-    if (old) {
-        c.uid = reinterpret_cast<const int64_t*>(slot + 2 * 64)[lane];
-        return;
-    }
-    c.pip = slot[2 * 64 + lane];
-    c.pmac = slot[3 * 64 + lane];
-    c.pp = slot[4 * 64 + lane];
-#pragma unroll
-    for (int k = 0; k < KDTN_NPROP; ++k) c.prop[k] = slot[(5 + k) * 64 + lane];
-    c.gap = slot[17 * 64 + lane];
-    c.uid = reinterpret_cast<const int64_t*>(slot + 18 * 64)[lane];
-}
-
 template <int V>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(var_waves(V))))
 k_reconcile(DevTopos T, DevLinks O, DevLinks N, DevTables tb, RecOut out, RecWork wk) {
@@ -2178,7 +1626,7 @@ k_reconcile(DevTopos T, DevLinks O, DevLinks N, DevTables tb, RecOut out, RecWor
     // look-backs — every chunk in the full prefix, or the comparison build, whose chunks past
     // it are deferred — the workgroup index serves and the single-address atomic (one per
     // workgroup) stays off every workgroup's critical path.
-    const bool need_ticket = (V & VAR_NO_PREFIX) != 0 || (!kDefer && fpi != 0u);
+    const bool need_ticket = !kDefer && fpi != 0u;
     if (need_ticket) {
         if (tid == 0) s.ticket = atomicAdd(&wk.sync[SYNC_TICKET], 1u);
         __syncthreads();
@@ -2242,7 +1690,7 @@ k_reconcile(DevTopos T, DevLinks O, DevLinks N, DevTables tb, RecOut out, RecWor
     // bulk: no topology of this workgroup has both lists non-empty (new pods: status empty;
     // deleted pods: spec nil) → every record of a DIFF topology is an entry, in order
     const bool bulk = s.any_cmp == 0;
-    const bool prefix = (V & VAR_NO_PREFIX) == 0 && wg <= ~fpi;
+    const bool prefix = wg <= ~fpi;
     const bool shared = bulk && prefix;                  // the parts split the records
     if (part != 0 && !shared) return;                    // (block-uniform)
     const bool lead = part == 0;
@@ -2266,11 +1714,6 @@ k_reconcile(DevTopos T, DevLinks O, DevLinks N, DevTables tb, RecOut out, RecWor
                                      wk.trace + (size_t)wg * TRACE_WORDS);
             else
                 diff_window_hb<false>(s, 0, nt, O, N, s.hash, s.flag, s.lt, s.tgt, wk.otarget);
-        } else if constexpr ((V & VAR_AB) != 0) {
-            if constexpr ((V & VAR_TRACE) != 0)
-                diff_window_ab<true>(s, 0, nt, O, N, s.hash, s.flag, s.lt, s.tgt, wk.trace + (size_t)wg * TRACE_WORDS);
-            else
-                diff_window_ab<false>(s, 0, nt, O, N, s.hash, s.flag, s.lt, s.tgt);
         } else if constexpr ((V & VAR_TRACE) != 0) {
             diff_window<true>(s, 0, nt, O, N, s.hash, s.flag, s.lt, s.tgt, wk.otarget, n0, wk.trace + (size_t)wg * TRACE_WORDS);
         } else {
@@ -2408,56 +1851,6 @@ k_reconcile(DevTopos T, DevLinks O, DevLinks N, DevTables tb, RecOut out, RecWor
 
     // ---- 4. emission -------------------------------------------------------------------
     uint2* stage = s.stage[tid >> 6];
-    if constexpr ((V & VAR_GLDS) != 0 && !kDefer) {
-        if (bulk) {
-            // Bulk emission from LDS-DMA'd tiles: the wave's tile is read from its slot, the
-            // record's gathers are issued, then the wave's next tile is copied into the slot
-            // (its reads have retired) while the gathers are in flight.
-            const int wave = tid >> 6, lane = tid & 63;
-            GlPlan pl = gl_plan(rlo, rhi, no, o0, n0);
-            // the plan in VGPRs: the emission's scalar registers hold the table bases
-            asm volatile("" : "+v"(pl.oa), "+v"(pl.ob), "+v"(pl.na), "+v"(pl.nb), "+v"(pl.to0), "+v"(pl.tn0));
-            uint32_t* slot = s.tiles[wave];
-            uint2* bst = s.bstage[wave];
-            gl_issue<NTL>(pl, (uint32_t)wave, O, N, slot, lane);
-            for (uint32_t g = wave; g < pl.nt; g += BLOCK / 64) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // the tile has landed
-                const bool old = g < pl.nto;
-                const uint32_t t = old ? pl.to0 + g : pl.tn0 + (g - pl.nto);
-                const uint32_t x = t * 64u + lane;
-                const bool in = old ? (x >= pl.oa && x < pl.ob) : (x >= pl.na && x < pl.nb);
-                int tt = 0;
-                bool on = false;
-                if (in) {
-                    tt = find_seg(old ? s.ooff : s.noff, 0, nt, x);
-                    on = s.act[tt] == KDTN_ACT_DIFF;
-                }
-                RecCols cc;
-                if (on) gl_cols(slot, lane, old, cc);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // slot reads retired
-                bool qa = false;
-                uint32_t e = 0, q[18];
-                const TopoCtx tc{s.ns[tt], s.src[tt], s.netns[tt]};
-                if (old) {
-                    gl_issue<NTL>(pl, g + BLOCK / 64, O, N, slot, lane);
-                    if (on) emit_del<V>(cc, x, tc, tb, out, bd + s.tcnt[0][tt] + (x - s.ooff[tt]), do_res);
-                } else {
-                    AddGath ga;
-                    if (on) add_gather<V>(cc, tc, tb, do_res, do_q, ga);
-                    gl_issue<NTL>(pl, g + BLOCK / 64, O, N, slot, lane);
-                    if (on) {
-                        e = ba + s.tcnt[2][tt] + (x - s.noff[tt]);
-                        add_finish<V | VAR_PMAC_COLS>(cc, ga, N, x, tc, tb, out, e, do_res, do_q, q);
-                        qa = do_q;
-                    }
-                }
-                wave_store_qdisc<V>(out.add_qdisc, qa, e, q, bst);
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            trace_mark<V>(wk, wg, 4);
-            return;
-        }
-    }
     if (bulk) {
         // Every record of a DIFF topology is an entry at topology offset + index. Software
         // pipelined: a thread's next record's columns are loaded right after this record's
@@ -2507,10 +1900,7 @@ k_reconcile(DevTopos T, DevLinks O, DevLinks N, DevTables tb, RecOut out, RecWor
         for (uint32_t b = rlo; b < rhi; b += BLOCK) {
             // the next record's segment search (LDS) runs after this record's gathers issue
             Slot nx;
-            if constexpr ((V & VAR_DECODE_FIRST) != 0) nx = decode(b + BLOCK + tid);
-            auto next = [&]() {
-                if constexpr ((V & VAR_DECODE_FIRST) == 0) nx = decode(b + BLOCK + tid);
-            };
+            auto next = [&]() { nx = decode(b + BLOCK + tid); };
             RecCols nc;
             bool qa = false;
             uint32_t e = 0, q[18];
@@ -2534,8 +1924,7 @@ k_reconcile(DevTopos T, DevLinks O, DevLinks N, DevTables tb, RecOut out, RecWor
                 next();
                 fetch(nx, nc);
             }
-            if constexpr ((V & VAR_Q16) != 0) wave_store_qdisc16<V>(out.add_qdisc, qa, e, q, s.stage64[tid >> 6]);
-            else wave_store_qdisc<V>(out.add_qdisc, qa, e, q, stage);
+            wave_store_qdisc<V>(out.add_qdisc, qa, e, q, stage);
             cs = nx;
             cc = nc;
         }

@@ -129,7 +129,7 @@ class Plan(C.Structure):
         "pstrings_parsed", "first_partial_chunk")]
 
 
-FRONT_SERIAL, FRONT_FUSED, FRONT_SIDE = 0, 1, 2
+FRONT_SERIAL, FRONT_FUSED, FRONT_SIDE = 0, 1, 2      # FRONT_SIDE: no longer produced
 PLACE_NONE, PLACE_WAVE, PLACE_PARTS = 0, 1, 2
 NO_PARTIAL_CHUNK = 0xFFFFFFFF
 

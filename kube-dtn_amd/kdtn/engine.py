@@ -760,7 +760,7 @@ class Engine:
         return {names[i].decode(): (float(ms[i]), int(ep[i])) for i in range(max(n, 0))}
 
     def wg_trace(self) -> np.ndarray:
-        """(nwg, 8) uint64 phase timestamps of the last traced run (KDTN_VARIANT bit 16)."""
+        """(nwg, 8) uint64 phase timestamps of the last traced run (KDTN_VARIANT trace bit, value 16)."""
         cap = 1 << 26
         buf = np.zeros(cap, np.uint64)
         n = lib().kdtn_debug_wg_trace(self._ctx, buf.ctypes.data_as(C.POINTER(C.c_uint64)), cap)

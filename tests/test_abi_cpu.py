@@ -80,7 +80,8 @@ def test_product_library_reads_no_environment():
     build, kube-dtn_amd/prof/libkdtn_prof.so)."""
     data = open(engine.LIB_PATH, "rb").read()
     for knob in (b"KDTN_VARIANT", b"KDTN_KD_SUB", b"KDTN_JS_VARIANT", b"KDTN_SPLIT", b"KDTN_PD_SPLIT",
-                 b"KDTN_PD_ONLY"):
+                 b"KDTN_PD_ONLY", b"KDTN_FUSE", b"KDTN_ALLOC_LOG", b"KDTN_SDMA_ENGINE", b"KDTN_DICT_FUSE",
+                 b"KDTN_LOOKUP_SIDE", b"KDTN_POD_PER"):
         assert knob not in data, knob
     names = set(re.findall(rb"_ZN4kdtn11k_reconcileILi(\d+)E", data))
     assert names == {b"16899", b"2116099"}, names   # default and comparison-heavy builds

@@ -1,7 +1,8 @@
 """Per-stage ablation of one reconcile epoch (one process, data generated once).
 
     python tools/ablate.py [--pods N] [--config C] [--reps R]
-(--variants / --env A/B runs load the profiling library: make -C kube-dtn_amd prof)
+(--variants / --env A/B runs load the profiling library: make -C kube-dtn_amd prof; without
+KDTN_VARIANT it launches the k_reconcile variant the product launches for the upload)
 Prints per-kernel HIP-event times for stage masks ALL, DIFF|RESOLVE, DIFF|QDISC, DIFF.
 """
 import argparse

@@ -1,6 +1,6 @@
 """A/B of the epoch front (profiling build): --knob KDTN_FUSE (0 the launches in sequence,
-1 the pod-table work fused into the dictionary-parse launches; round 3 also measured KDTN_SIDE,
-a side stream for the tables, since removed: profiles/r03u_side_ab.json). Config-2 epochs at
+1 the pod-table work fused into the dictionary-parse launches; a side stream for the tables was
+measured too and its code removed: profiles/r03u_side_ab.json). Config-2 epochs at
 timing level 0, modes interleaved, median wall time of run + sync per epoch; every mode must
 produce the same epoch.
 Usage: python tools/side_ab.py [--pods 1000000] [--reps 30] [--knob KDTN_FUSE] [--modes 0,1]"""

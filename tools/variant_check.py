@@ -1,10 +1,13 @@
-"""Output equality of k_reconcile profiling variants against the default build (one process).
+"""Output equality of k_reconcile profiling variants against what the product launches (one process).
 
-    python tools/variant_check.py --variants 66051,65539 [--config 2] [--pods N]
-Loads the profiling library (make -C kube-dtn_amd prof); for each workload runs the default
-variant, downloads every output array, then each listed variant and compares the arrays
-bit for bit. Prints one JSON line per (workload, variant). A variant that is A/B-timed by
-tools/ablate.py must pass this first.
+    python tools/variant_check.py --variants 16899,2116099,519 [--configs 2,3:20000] [--random N]
+Loads the profiling library (make -C kube-dtn_amd prof); for each workload runs with KDTN_VARIANT
+unset — the variant the product library picks for that upload (DIFF_VARIANT when both link
+lists are non-empty, else DEFAULT_VARIANT) — downloads every output array, then each listed
+variant and compares the arrays bit for bit. Prints one JSON line per (workload, variant); a
+variant the run rejects (not instantiated, or the comparison build on an upload without
+realised links) is reported with its error. A variant that is A/B-timed by tools/ablate.py must
+pass this first.
 """
 import argparse
 import json
@@ -70,10 +73,14 @@ for name, inp in workloads():
     for stages in (abi.STAGE_ALL, abi.STAGE_DIFF | abi.STAGE_RESOLVE, abi.STAGE_DIFF | abi.STAGE_QDISC):
         want = outputs(eng, None, stages)
         for v in a.variants.split(","):
-            bad = compare(want, outputs(eng, int(v), stages))
-            ok &= not bad
-            print(json.dumps({"workload": name, "stages": stages, "variant": int(v), "equal": not bad,
-                              "differs": bad}), flush=True)
+            line = {"workload": name, "stages": stages, "variant": int(v)}
+            try:
+                bad = compare(want, outputs(eng, int(v), stages))
+                line.update(equal=not bad, differs=bad)
+            except _eng.KdtnError as e:
+                line.update(equal=False, error=str(e))
+            ok &= line["equal"]
+            print(json.dumps(line), flush=True)
 os.environ.pop("KDTN_VARIANT", None)
 eng.close()
 sys.exit(0 if ok else 1)

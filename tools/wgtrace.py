@@ -1,4 +1,4 @@
-"""Per-workgroup phase timeline of k_reconcile (KDTN_VARIANT bit 16 build of the kernel).
+"""Per-workgroup phase timeline of k_reconcile (a KDTN_VARIANT with the trace bit, value 16).
 
     python tools/wgtrace.py [--pods N] [--config C] [--variant V] [--out file.npy]
 Phases: 0 entry → 1 topologies loaded → 2 counts done → 3 batch bases (look-back) → 4 end.
