@@ -33,6 +33,9 @@
  *   kdtn_remote_ingest    replaces, on the daemon that receives those bodies, proto.Unmarshal into
  *                         pb.RemotePod and the pure prefix of KubeDTN.Update
  *                         (daemon/kubedtn/handler.go:149-198) for a batch of them
+ *   kdtn_update_ingest    replaces proto.Unmarshal and the pure part of Local.UpdateLinks
+ *                         (daemon/kubedtn/handler.go:634-657: MakeVeth, MakeQdiscs and the
+ *                         first-error abort per link) for a batch of request bodies
  *   kdtn_epoch_late_pods  getPod's API-server fallback on an informer miss
  *                         (daemon/kubedtn/handler.go:35-39): late pod rows for the lookup
  *
@@ -663,8 +666,9 @@ int kdtn_epoch_tables_info(kdtn_ctx* ctx, kdtn_ingest_info* info);
  *     realised list empty and non-nil; KDTN_BATCH_DEL: the links are its realised segment, the
  *     desired list empty and non-nil. With the gate and CalcDiff an ADD message comes out of
  *     kdtn_epoch_run as one add batch and a DEL message as one del batch, planned as the
- *     daemon's handler would. Planning UPD messages (UpdateLinks: MakeQdiscs per link) is not
- *     done by the epoch run: it stays with kdtn_make_qdiscs over the decoded tables;
+ *     daemon's handler would. UPD messages (UpdateLinks: MakeVeth and MakeQdiscs per link) are
+ *     decoded here, not planned by the epoch run: kdtn_update_ingest plans them from the same
+ *     request bodies in one pass;
  *   - a rejected message (err[m] != 0) is a Topology with both lists and its four strings empty;
  *     decoding goes on with the next message (per-message errors are data, not return codes).
  * Dictionaries as kdtn_json_ingest leaves them: id 0 = "", no duplicates, ids ranked by the
@@ -779,6 +783,79 @@ typedef struct kdtn_remote_ingest_plan_t {
     uint32_t n_conflict;      /* messages with vni_conflict set */
 } kdtn_remote_ingest_plan_t;
 int kdtn_remote_ingest_plan(kdtn_ctx* ctx, kdtn_remote_ingest_plan_t* out);
+
+/* ---- daemon-side ingest: UpdateLinks bodies → per-link plans ------------------------------ */
+/* The request bodies of Local.UpdateLinks (daemon/kubedtn/handler.go:634-671) decoded and
+ * planned on the GPU in one pass: per link the pure part of the handler's loop body,
+ * MakeVeth(localPod.NetNs, LocalIntf, LocalIp, LocalMac) (common/veth.go:13-41) and
+ * MakeQdiscs(Properties) (common/qdisc.go:20-126); per message the handler's first-error abort,
+ * as data. UpdateLinks reads no pod table, VXLAN map or dictionary, so nothing is interned and
+ * the call leaves the context's epoch state (tables, outputs, resident map) as it was.
+ * The stream goes up with kdtn_json_upload; message m = stream[off[m], off[m+1]) under
+ * kdtn_wire_in's rules for off. n_msgs == 0 and messages without links are valid.
+ * Decoding is kdtn_wire_ingest's, letter for letter (fields in any order, unknown numbers and
+ * wrong wire types skipped, the last scalar wins, properties and local_pod occurrences merge,
+ * links append, every string in a known field valid UTF-8, groups refused, a Pod.links element
+ * nested in local_pod decoded for its errors only, the lowest-offset fault among those the
+ * passes meet wins): wire_err is what kdtn_wire_ingest's err[m] would be.
+ * Per link: err = KDTN_E_VETH_CIDR when LocalIp != "" and net.ParseCIDR fails, else
+ * KDTN_E_VETH_MAC when LocalMac != "" and net.ParseMAC fails, else the first failing MakeQdiscs
+ * step (KDTN_E_LATENCY … KDTN_E_RATE), else 0: the order of handler.go:649-657. qdisc[i] =
+ * MakeQdiscs(properties) whatever MakeVeth says: what kdtn_make_qdiscs returns for the same
+ * twelve strings and gap (absent properties: the empty record, like nil). Every link of an
+ * accepted message gets its plan, the ones after the cut too: the cut is data.
+ * Per message: its plans are link[link_base .. link_base + n_links) in stream order; cut is the
+ * index within the message of the first link with err != 0 (n_links: none): the handler applies
+ * links [0, cut) and returns link cut's error, err. A rejected message (wire_err != 0) has
+ * n_links = 0, cut = 0 and every other field 0, reports no plans, and does not disturb its
+ * neighbours (link_base stays the running sum of n_links).
+ * Results: msg[n_msgs] always; link and qdisc (qdisc may be NULL) when link_cap >= the batch's
+ * n_links, which the call stores in out->n_links either way. The records stay on the device
+ * until the next kdtn_update_ingest: call again with in = NULL and larger arrays to fetch them
+ * (KDTN_EINVAL when there is no batch to fetch). */
+typedef struct kdtn_update_msg {           /* 32 bytes per message */
+    kdtn_remote_str net_ns, name;          /* LocalPod.NetNs / Name: the surviving values (absent: empty) */
+    uint32_t link_base, n_links;
+    uint32_t cut;
+    uint8_t  wire_err;                     /* kdtn_wire_err */
+    uint8_t  err;                          /* kdtn_err of link cut, 0 when cut == n_links */
+    uint16_t reserved;
+} kdtn_update_msg;
+typedef struct kdtn_update_link {          /* 32 bytes per link */
+    kdtn_remote_str local_intf;            /* the device name; everything else is in the qdisc record */
+    int64_t  uid;                          /* the 64-bit varint as two's complement */
+    uint32_t msg, index;                   /* its message, and its index within it */
+    uint8_t  err;                          /* kdtn_err, above */
+    uint8_t  has_props;                    /* a properties field was present */
+    uint16_t reserved0;
+    uint32_t reserved;
+} kdtn_update_link;
+typedef struct kdtn_update_in {
+    uint32_t        n_msgs;
+    const uint64_t* off;       /* [n_msgs+1] message m = stream[off[m], off[m+1]) */
+} kdtn_update_in;
+typedef struct kdtn_update_out {
+    kdtn_update_msg*  msg;     /* [n_msgs] */
+    kdtn_update_link* link;    /* [link_cap] */
+    kdtn_qdisc*       qdisc;   /* [link_cap], may be NULL */
+    uint32_t          link_cap;
+    uint32_t          n_links; /* out: the plans of the batch */
+} kdtn_update_out;
+int kdtn_update_ingest(kdtn_ctx* ctx, const kdtn_update_in* in, kdtn_update_out* out);
+/* What the last kdtn_update_ingest did (read-only report): the frame pass is kdtn_wire_ingest's
+ * (n_long: messages that took a whole wave there); the plan pass walks each wave's 64 link
+ * frames from a window of window_bytes of on-chip memory, and n_direct counts the frames walked
+ * from memory instead: a Link that does not fit one window ((offset & 15) + length >
+ * window_bytes). */
+typedef struct kdtn_update_ingest_plan_t {
+    uint32_t window_bytes;
+    uint32_t n_long;
+    uint32_t n_direct;
+    uint32_t n_rejected;      /* messages with wire_err != 0 */
+    uint32_t n_links;         /* plans reported */
+    uint32_t n_cut;           /* messages with cut < n_links */
+} kdtn_update_ingest_plan_t;
+int kdtn_update_ingest_plan(kdtn_ctx* ctx, kdtn_update_ingest_plan_t* out);
 
 /* Sharded ingest for one rank of nshards (SURVEY §8(e) with §8(f) rank 2). Every controller
  * replica's informer holds the whole Topology store (the controller watches all Topologies,

@@ -248,6 +248,12 @@ struct kdtn_ctx : kdtn_ctx_handles {
     DevBuf ri_start, ri_size, ri_vni, ri_nsb, ri_nso, ri_slots, ri_plan, ri_qd, ri_ctl;
     kdtn_remote_ingest_plan_t ri_report{};
     bool ri_done = false;
+    // UpdateLinks planning (kdtn_update_ingest; its frame pass works in the u_* lists above): cut
+    // words, counts and their scan, staged and placed records, report
+    DevBuf ul_cut, ul_cnt, ul_base64, ul_link0, ul_qd0, ul_msg, ul_link, ul_qd, ul_ctl;
+    kdtn_update_ingest_plan_t ul_report{};
+    uint32_t ul_T = 0;
+    bool ul_done = false;
     kdtn_ingest_info j_info{};
     bool uploaded = false;
     bool ran = false;

@@ -1,5 +1,5 @@
 // kdtn_engine_ingest.hip — the ingest entry points of the C-ABI: TopologyList JSON, LinksBatchQuery streams,
-// RemotePod bodies, the sharded ingest, and the ingested tables' download
+// RemotePod bodies, UpdateLinks bodies, the sharded ingest, and the ingested tables' download
 // (host side of libkdtn.so; the context and the shared helpers are in kdtn_engine.h)
 #include "kdtn_engine.h"
 
@@ -441,6 +441,54 @@ int kdtn_json_ingest(kdtn_ctx* c, const kdtn_vni_table* vnis, kdtn_ingest_info* 
     return json_ingest_full(c, vnis, info);
 }
 
+// The frame pass of a stream of LinksBatchQuery messages (k_uw_frame<0/1>, kdtn_unwire.hip), for
+// kdtn_wire_ingest and kdtn_update_ingest: the message table up, the count pass and its scans,
+// one host round trip for the frame totals, the lists sized and written. Leaves the views of
+// the stream and of the lists in *ui / *fr (merr holds the top-level faults).
+static int wire_frames(kdtn_ctx* c, const char* who, uint32_t T, const uint64_t* off, const uint8_t* kind_dev, UwIn* ui,
+                       UwFrames* fr, uint32_t* n_link_frames, uint32_t* n_pod_frames) {
+    hipStream_t s = c->stream;
+    TRY(ensure(c->u_off, ((size_t)T + 1) * 8));
+    for (DevBuf* b : {&c->u_nl, &c->u_np}) TRY(ensure(*b, (size_t)T * 4));
+    for (DevBuf* b : {&c->u_loff, &c->u_poff, &c->u_merr}) TRY(ensure(*b, ((size_t)T + 1) * 8));
+    TRY(ensure(c->u_ctl, UW_CTL_WORDS * 8));
+    if (T) HIP_TRY(hipMemcpyAsync(c->u_off.p, off, ((size_t)T + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(c->u_merr.p, 0xFF, ((size_t)T + 1) * 8, s));
+    HIP_TRY(hipMemsetAsync(c->u_ctl.p, 0, UW_CTL_WORDS * 8, s));
+    HIP_TRY(hipMemsetAsync(dp<unsigned long long>(c->u_ctl) + UW_CTL_FIRST_LONG, 0xFF, 8, s));
+    *ui = UwIn{dp<uint8_t>(c->j_doc), (uint32_t)c->j_n, (uint32_t)((size_t)c->j_nb * 64 + 128), T,
+               dp<uint64_t>(c->u_off), kind_dev};
+    *fr = UwFrames{dp<uint32_t>(c->u_nl), dp<uint32_t>(c->u_np), dp<uint64_t>(c->u_loff), dp<uint64_t>(c->u_poff),
+                   nullptr, nullptr, nullptr, dp<unsigned long long>(c->u_merr), dp<unsigned long long>(c->u_ctl)};
+    const uint32_t nwave = nblocks(T, 64);
+    if (T) k_uw_frame<false><<<nwave, UW_BLOCK, 0, s>>>(*ui, *fr);
+    TRY(scan_u32(c, fr->nl, T, dp<uint64_t>(c->u_loff)));
+    TRY(scan_u32(c, fr->np, T, dp<uint64_t>(c->u_poff)));
+    timer_mark(c, "uw_frame_count");
+    uint64_t nlf64 = 0, npf64 = 0;
+    TRY(d2h(c, &nlf64, fr->loff + T));
+    TRY(d2h(c, &npf64, fr->poff + T));
+    HIP_TRY(hipStreamSynchronize(s));
+    timer_mark(c, "uw_sync");
+    HIP_TRY(hipGetLastError());
+    if (nlf64 >= 0xFFFFFFFFull || npf64 >= 0xFFFFFFFFull) {
+        std::snprintf(g_last_error, sizeof(g_last_error), "%s: too many links for one stream", who);
+        return KDTN_EINVAL;
+    }
+    const uint32_t NF = (uint32_t)nlf64, NP = (uint32_t)npf64;
+    TRY(ensure(c->u_lfr, (size_t)NF * 8));
+    TRY(ensure(c->u_lmsg, (size_t)NF * 4));
+    TRY(ensure(c->u_pfr, (size_t)NP * 8));
+    fr->lfr = dp<uint2>(c->u_lfr);
+    fr->lmsg = dp<uint32_t>(c->u_lmsg);
+    fr->pfr = dp<uint2>(c->u_pfr);
+    if (T) k_uw_frame<true><<<nwave, UW_BLOCK, 0, s>>>(*ui, *fr);
+    timer_mark(c, "uw_frame_write");
+    *n_link_frames = NF;
+    *n_pod_frames = NP;
+    return KDTN_OK;
+}
+
 // LinksBatchQuery streams → the context's epoch tables (kdtn_unwire.hip). Host round trips:
 // the frame totals (to size the frame lists), the record totals with the error bytes (to size
 // the stores), the intern status (again only when a table is grown), then the dictionary finish's.
@@ -469,49 +517,19 @@ int kdtn_wire_ingest(kdtn_ctx* c, const kdtn_wire_in* in, kdtn_ingest_info* info
     stage_begin(c);
     const JsTargets tg = ingest_targets(c);
 
-    // 1. the message table, the top-level count pass and its scans
-    TRY(ensure(c->u_off, ((size_t)T + 1) * 8));
+    // 1. the message table and the frame pass
+    for (DevBuf* b : {&c->u_cdes, &c->u_creal, &c->u_rbase}) TRY(ensure(*b, (size_t)T * 4));
+    for (DevBuf* b : {&c->u_des64, &c->u_real64}) TRY(ensure(*b, ((size_t)T + 1) * 8));
     TRY(ensure(c->u_kind, (size_t)T));
-    for (DevBuf* b : {&c->u_nl, &c->u_np, &c->u_cdes, &c->u_creal, &c->u_rbase}) TRY(ensure(*b, (size_t)T * 4));
-    for (DevBuf* b : {&c->u_loff, &c->u_poff, &c->u_des64, &c->u_real64, &c->u_merr}) TRY(ensure(*b, ((size_t)T + 1) * 8));
     TRY(ensure(c->u_err8, (size_t)T));
-    TRY(ensure(c->u_ctl, UW_CTL_WORDS * 8));
     TRY(ensure(c->j_small, J_SMALL));
-    if (T) {
-        HIP_TRY(hipMemcpyAsync(c->u_off.p, in->off, ((size_t)T + 1) * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(c->u_kind.p, in->kind, T, hipMemcpyHostToDevice, s));
-    }
-    HIP_TRY(hipMemsetAsync(c->u_merr.p, 0xFF, ((size_t)T + 1) * 8, s));
-    HIP_TRY(hipMemsetAsync(c->u_ctl.p, 0, UW_CTL_WORDS * 8, s));
-    HIP_TRY(hipMemsetAsync(dp<unsigned long long>(c->u_ctl) + UW_CTL_FIRST_LONG, 0xFF, 8, s));
-    const UwIn ui{dp<uint8_t>(c->j_doc), (uint32_t)c->j_n, (uint32_t)((size_t)c->j_nb * 64 + 128), T,
-                  dp<uint64_t>(c->u_off), dp<uint8_t>(c->u_kind)};
-    UwFrames fr{dp<uint32_t>(c->u_nl), dp<uint32_t>(c->u_np), dp<uint64_t>(c->u_loff), dp<uint64_t>(c->u_poff),
-                nullptr, nullptr, nullptr, dp<unsigned long long>(c->u_merr), dp<unsigned long long>(c->u_ctl)};
-    const uint32_t nwave = nblocks(T, 64);
-    if (T) k_uw_frame<false><<<nwave, UW_BLOCK, 0, s>>>(ui, fr);
-    TRY(scan_u32(c, fr.nl, T, dp<uint64_t>(c->u_loff)));
-    TRY(scan_u32(c, fr.np, T, dp<uint64_t>(c->u_poff)));
-    timer_mark(c, "uw_frame_count");
-    uint64_t nlf64 = 0, npf64 = 0;
-    TRY(d2h(c, &nlf64, fr.loff + T));
-    TRY(d2h(c, &npf64, fr.poff + T));
-    HIP_TRY(hipStreamSynchronize(s));
-    timer_mark(c, "uw_sync");
-    HIP_TRY(hipGetLastError());
-    if (nlf64 >= 0xFFFFFFFFull || npf64 >= 0xFFFFFFFFull) {
-        std::snprintf(g_last_error, sizeof(g_last_error), "kdtn_wire_ingest: too many links for one stream");
-        return KDTN_EINVAL;
-    }
-    const uint32_t NF = (uint32_t)nlf64, NP = (uint32_t)npf64;
+    if (T) HIP_TRY(hipMemcpyAsync(c->u_kind.p, in->kind, T, hipMemcpyHostToDevice, s));
+    UwIn ui{};
+    UwFrames fr{};
+    uint32_t NF = 0, NP = 0;
+    TRY(wire_frames(c, "kdtn_wire_ingest", T, in->off, dp<uint8_t>(c->u_kind), &ui, &fr, &NF, &NP));
 
-    // 2. frames, then the nested decode for its errors; record counts per side
-    TRY(ensure(c->u_lfr, (size_t)NF * 8));
-    TRY(ensure(c->u_lmsg, (size_t)NF * 4));
-    TRY(ensure(c->u_pfr, (size_t)NP * 8));
-    fr.lfr = dp<uint2>(c->u_lfr);
-    fr.lmsg = dp<uint32_t>(c->u_lmsg);
-    fr.pfr = dp<uint2>(c->u_pfr);
+    // 2. the nested decode for its errors; record counts per side
     for (DevBuf* b : {tg.ns, tg.name, tg.src, tg.netns, &c->j_tflags}) TRY(ensure(*b, (size_t)T * 4));
     TRY(ensure(*tg.flags, (size_t)T));
     TRY(ensure(*tg.roff, ((size_t)T + 1) * 4));
@@ -520,8 +538,6 @@ int kdtn_wire_ingest(kdtn_ctx* c, const kdtn_wire_in* in, kdtn_ingest_info* info
                  dp<uint32_t>(c->j_tflags), dp<uint32_t>(*tg.roff), dp<uint32_t>(*tg.noff)};
     JsIntern it{};
     const JsStore none{nullptr};
-    if (T) k_uw_frame<true><<<nwave, UW_BLOCK, 0, s>>>(ui, fr);
-    timer_mark(c, "uw_frame_write");
     if (NF) k_uw_links<false><<<nblocks(NF, 64), UW_BLOCK, 0, s>>>(ui, fr, NF, nullptr, none, none, it);
     if (T) k_uw_pods<false><<<nblocks(T), BLOCK, 0, s>>>(ui, fr, to, it);
     timer_mark(c, "uw_check");
@@ -699,6 +715,97 @@ int kdtn_remote_ingest(kdtn_ctx* c, const kdtn_remote_in* in, kdtn_remote_plan* 
 int kdtn_remote_ingest_plan(kdtn_ctx* c, kdtn_remote_ingest_plan_t* out) {
     if (!c || !out || !c->ri_done) return KDTN_EINVAL;
     *out = c->ri_report;
+    return KDTN_OK;
+}
+
+// Copies of the last batch's records to the caller (the records stay in ul_msg / ul_link / ul_qd)
+static int update_fetch(kdtn_ctx* c, kdtn_update_out* out, uint32_t n_links) {
+    hipStream_t s = c->stream;
+    const uint32_t T = c->ul_T;
+    if (T) HIP_TRY(hipMemcpyAsync(out->msg, c->ul_msg.p, (size_t)T * sizeof(kdtn_update_msg), hipMemcpyDeviceToHost, s));
+    if (n_links && out->link)
+        HIP_TRY(hipMemcpyAsync(out->link, c->ul_link.p, (size_t)n_links * sizeof(kdtn_update_link), hipMemcpyDeviceToHost, s));
+    if (n_links && out->link && out->qdisc)
+        HIP_TRY(hipMemcpyAsync(out->qdisc, c->ul_qd.p, (size_t)n_links * sizeof(kdtn_qdisc), hipMemcpyDeviceToHost, s));
+    return KDTN_OK;
+}
+
+// UpdateLinks bodies → per-link plans (kdtn_update.hip). One host round trip inside the call,
+// the frame totals that size the lists; the report block and the records come back together at
+// the end. The placed records hold at most one per link frame, so their copies are enqueued
+// before the surviving count is known. Touches only the frame pass's lists, its own buffers
+// and the uploaded bytes: the context's epoch state stays as it was.
+int kdtn_update_ingest(kdtn_ctx* c, const kdtn_update_in* in, kdtn_update_out* out) {
+    if (!c || !out) return KDTN_EINVAL;
+    g_last_error[0] = 0;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    if (!in) {                                               // the last batch's records again
+        if (!c->ul_done || (c->ul_T && !out->msg)) return KDTN_EINVAL;
+        out->n_links = c->ul_report.n_links;
+        StreamsDrain drain{s, s};
+        TRY(update_fetch(c, out, out->link_cap >= out->n_links ? out->n_links : 0u));
+        HIP_TRY(hipStreamSynchronize(s));
+        drain.armed = false;
+        return KDTN_OK;
+    }
+    const uint32_t T = in->n_msgs;
+    if (!c->j_loaded || (T && (!in->off || !out->msg))) return KDTN_EINVAL;
+    for (uint32_t m = 0; m < T; ++m) {
+        if (in->off[m + 1] < in->off[m] || in->off[m + 1] > c->j_n) {
+            std::snprintf(g_last_error, sizeof(g_last_error),
+                          "kdtn_update_ingest: message %u: offsets must ascend within the uploaded %llu bytes", m,
+                          (unsigned long long)c->j_n);
+            return KDTN_EINVAL;
+        }
+    }
+    c->ul_done = false;
+    StreamsDrain drain{s, s};                                // (the copies below read caller memory)
+    stage_begin(c);
+    UwIn ui{};
+    UwFrames fr{};
+    uint32_t NF = 0, NP = 0;
+    TRY(wire_frames(c, "kdtn_update_ingest", T, in->off, nullptr, &ui, &fr, &NF, &NP));
+
+    TRY(ensure(c->ul_cut, (size_t)T * 8));
+    TRY(ensure(c->ul_cnt, (size_t)T * 4));
+    TRY(ensure(c->ul_base64, ((size_t)T + 1) * 8));
+    TRY(ensure(c->ul_msg, (size_t)T * sizeof(kdtn_update_msg)));
+    for (DevBuf* b : {&c->ul_link0, &c->ul_link}) TRY(ensure(*b, (size_t)NF * sizeof(kdtn_update_link)));
+    for (DevBuf* b : {&c->ul_qd0, &c->ul_qd}) TRY(ensure(*b, (size_t)NF * sizeof(kdtn_qdisc)));
+    TRY(ensure(c->ul_ctl, UL_CTL_WORDS * 4));
+    if (T) HIP_TRY(hipMemsetAsync(c->ul_cut.p, 0xFF, (size_t)T * 8, s));
+    HIP_TRY(hipMemsetAsync(c->ul_ctl.p, 0, UL_CTL_WORDS * 4, s));
+    const UlOut uo{dp<uint4>(c->ul_link0), dp<uint2>(c->ul_qd0), dp<unsigned long long>(c->ul_cut), dp<uint32_t>(c->ul_ctl)};
+    if (NF) k_ul_plan<<<nblocks(NF, 64), UW_BLOCK, 0, s>>>(ui, fr, NF, c->cfg.tick_in_usec, uo);
+    timer_mark(c, "ul_plan");
+    if (T) k_ul_msgs<<<nblocks(T), BLOCK, 0, s>>>(ui, fr, uo, dp<uint4>(c->ul_msg), dp<uint32_t>(c->ul_cnt));
+    TRY(scan_u32(c, dp<uint32_t>(c->ul_cnt), T, dp<uint64_t>(c->ul_base64)));
+    const uint64_t nthr = std::max<uint64_t>(13ull * NF, T);
+    if (nthr) k_ul_pack<<<nblocks(nthr), BLOCK, 0, s>>>(fr, T, NF, dp<uint64_t>(c->ul_base64), uo, dp<uint4>(c->ul_msg),
+                                                       dp<uint2>(c->ul_link), dp<uint2>(c->ul_qd));
+    timer_mark(c, "ul_msgs");
+    HIP_TRY(hipGetLastError());
+    uint32_t ctl[UL_CTL_WORDS] = {};
+    unsigned long long wctl[UW_CTL_WORDS] = {};
+    uint64_t nl64 = 0;
+    TRY(d2h(c, ctl, c->ul_ctl.p, UL_CTL_WORDS));
+    TRY(d2h(c, wctl, c->u_ctl.p, UW_CTL_WORDS));
+    TRY(d2h(c, &nl64, dp<uint64_t>(c->ul_base64) + T));
+    c->ul_T = T;
+    TRY(update_fetch(c, out, std::min(NF, out->link_cap)));
+    HIP_TRY(hipStreamSynchronize(s));
+    drain.armed = false;
+    out->n_links = (uint32_t)nl64;
+    c->ul_report = kdtn_update_ingest_plan_t{UW_WIN, (uint32_t)wctl[UW_CTL_N_LONG], ctl[UL_CTL_DIRECT], ctl[UL_CTL_REJECTED],
+                                             (uint32_t)nl64, ctl[UL_CTL_CUT]};
+    c->ul_done = true;
+    return KDTN_OK;
+}
+
+int kdtn_update_ingest_plan(kdtn_ctx* c, kdtn_update_ingest_plan_t* out) {
+    if (!c || !out || !c->ul_done) return KDTN_EINVAL;
+    *out = c->ul_report;
     return KDTN_OK;
 }
 

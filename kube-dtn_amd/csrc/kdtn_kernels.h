@@ -837,6 +837,19 @@ struct RpIn {
 __global__ void k_rp_vni_build(const int32_t* vni, uint32_t n, uint32_t* slots, uint32_t mask, uint32_t shift);
 __global__ void k_rp_plan(RpIn in, uint4* plan, uint2* qdisc, uint32_t* ctl);
 
+// ---- UpdateLinks bodies → per-link plans (kdtn_update.hip), after k_uw_frame<0/1> -----------
+enum : int { UL_CTL_DIRECT = 0, UL_CTL_REJECTED = 1, UL_CTL_CUT = 2, UL_CTL_WORDS = 4 };   // the report block
+struct UlOut {
+    uint4* link;               // plans staged at the frame's index, 32 B each
+    uint2* qdisc;              // qdisc records staged at the frame's index, 72 B each
+    unsigned long long* mcut;  // [n_msgs] lowest (index in message << 8 | err) of a failing link, ~0 = none
+    uint32_t* ctl;             // UL_CTL_*
+};
+__global__ void k_ul_plan(UwIn in, UwFrames f, uint32_t nfr, double tick, UlOut o);
+__global__ void k_ul_msgs(UwIn in, UwFrames f, UlOut o, uint4* msg, uint32_t* cnt);
+__global__ void k_ul_pack(UwFrames f, uint32_t n_msgs, uint32_t nfr, const uint64_t* base64, UlOut o, uint4* msg,
+                          uint2* link, uint2* qdisc);
+
 // sharded ingest (kdtn_json_ingest_shard): keep[t] = this shard owns topology t; then the
 // kept topologies' columns and records compacted into fresh tables (document order kept)
 __global__ void k_shard_mark(DevTopos T, const uint8_t* kd_bytes, const uint32_t* kd_offs, uint32_t nshards,

@@ -15,12 +15,12 @@
 //                    pairs, vni, the merged properties' twelve pairs and gap, all in registers —
 //                    then parses the strings it needs in place (cidr_ok, and the kdtn_parse.h
 //                    parsers from a loop with three call sites), composes the qdisc record as
-//                    qdisc_from does, probes the VNI table and compares the netns bytes. Plans
+//                    qdisc_from does (kdtn_qplan.h), probes the VNI table and compares the netns bytes. Plans
 //                    and qdisc records of the wave are staged in LDS and stored coalesced.
 // A body that does not fit the window, and every body of a wave whose starts are not ascending
 // or leave a gap of more than a window, is walked from memory instead (UwWin falls back to
 // memory for any byte outside the staged range, so the result never depends on the window).
-#include "kdtn_wirewalk.h"
+#include "kdtn_qplan.h"
 
 namespace kdtn {
 
@@ -86,56 +86,6 @@ KD_INLINE uint32_t rp_walk(const UwWin& w, uint32_t a, uint32_t e, RpMsg& M) {
     return KDTN_WIRE_OK;
 }
 
-// The twelve property strings parsed where they lie: what k_pdict_parse leaves in the parsed
-// tables for the same bytes ("" parses to 0 everywhere), and the columns that failed.
-struct RpVals {
-    uint32_t v[KDTN_NPROP];          // duration µs, Percentage2u32, the rate's low word
-    uint32_t lat_t, jit_t, rate_hi;  // time2Tick of the two durations, the rate's high word
-    uint32_t bad;                    // bit k: column k failed to parse
-};
-
-// MakeQdiscs over parsed values: qdisc_from's sibling (same error order, NewNetem conditionals
-// and TBF burst; common/qdisc.go:20-126 + netlink NewNetem), for values parsed per message
-// instead of gathered from the dictionary tables.
-KD_INLINE void qdisc_from_parsed(const RpVals& p, uint32_t gap, bool empty, uint32_t* q) {
-#pragma unroll
-    for (int w = 0; w < 18; ++w) q[w] = 0;
-    if (empty) return;
-    if (p.bad) {
-        // reference order: columns 0-4, then 6-11, the rate (5) last = KDTN_E_LATENCY … KDTN_E_RATE
-        const uint32_t ord = (p.bad & 0x1Fu) | ((p.bad >> 6) << 5) | (((p.bad >> 5) & 1u) << 11);
-        q[17] = ((uint32_t)KDTN_E_LATENCY + (uint32_t)__builtin_ctz(ord)) << 16;   // byte 70 = err
-        return;
-    }
-    const uint32_t lat_us = p.v[KDTN_P_LATENCY], jit_us = p.v[KDTN_P_JITTER];
-    const uint32_t los = p.v[KDTN_P_LOSS], dup = p.v[KDTN_P_DUPLICATE], rop = p.v[KDTN_P_REORDER_PROB];
-    q[0] = p.lat_t;                                                     // latency
-    q[1] = (lat_us > 0 && jit_us > 0) ? p.v[KDTN_P_LATENCY_CORR] : 0u;  // delay_corr
-    q[2] = 1000u;                                                       // limit
-    q[3] = los;                                                         // loss
-    q[4] = los > 0 ? p.v[KDTN_P_LOSS_CORR] : 0u;                        // loss_corr
-    q[5] = (rop > 0 && gap == 0) ? 1u : gap;                            // gap
-    q[6] = dup;                                                         // duplicate
-    q[7] = dup > 0 ? p.v[KDTN_P_DUPLICATE_CORR] : 0u;                   // duplicate_corr
-    q[8] = p.lat_t > 0 ? p.jit_t : jit_us;                              // jitter
-    q[9] = rop;
-    q[10] = p.v[KDTN_P_REORDER_CORR];
-    q[11] = p.v[KDTN_P_CORRUPT_PROB];
-    q[12] = p.v[KDTN_P_CORRUPT_CORR];
-    const uint64_t rate = ((uint64_t)p.rate_hi << 32) | p.v[KDTN_P_RATE];
-    uint32_t has_tbf = 0;
-    if (rate != 0) {
-        uint32_t burst = (uint32_t)(rate / 250ull);                     // getTbfBurst
-        if (burst < 5000u) burst = 5000u;
-        q[13] = burst;
-        q[14] = p.v[KDTN_P_RATE];
-        q[15] = p.rate_hi;
-        q[16] = 1500u;
-        has_tbf = 1;
-    }
-    q[17] = 1u | (has_tbf << 8);                                        // has_netem, has_tbf, err = 0
-}
-
 KD_INLINE uint32_t rp_home(uint32_t vni, uint32_t shift) { return (vni * 0x9E3779B1u) >> shift; }
 
 // Open addressing over the snapshot, keyed by vni: a slot holds an entry index, RP_EMPTY when
@@ -166,16 +116,6 @@ KD_INLINE uint32_t rp_lookup(const RpIn& in, uint32_t vni) {
     return RP_EMPTY;
 }
 
-// all lanes of the (one-wave) workgroup: stage [base, base + lim) (both multiples of 16)
-KD_INLINE void rp_fill(uint4* win, const RpIn& in, UwWin& w, uint32_t base, uint32_t lim) {
-    __syncthreads();                                        // the previous window's readers
-    const uint4* src = reinterpret_cast<const uint4*>(in.doc + base);
-    for (uint32_t i = threadIdx.x; i < lim / 16; i += UW_BLOCK) win[i] = src[i];
-    __syncthreads();
-    w.base = base;
-    w.lim = lim;
-}
-
 // One message: the walk, then the plan (16 dwords at P) and the qdisc record (18 dwords at Q),
 // both in the wave's LDS images. wbytes: the window as bytes, for the parsers.
 KD_INLINE void rp_one(const RpIn& in, const UwWin& w, const uint8_t* wbytes, uint32_t a, uint32_t e, uint32_t* P,
@@ -199,52 +139,8 @@ KD_INLINE void rp_one(const RpIn& in, const UwWin& w, const uint8_t* wbytes, uin
     uint32_t err = 0;
     if (M.sl[KDTN_RP_INTF_IP] && !cidr_ok(at(M.so[KDTN_RP_INTF_IP]), M.sl[KDTN_RP_INTF_IP])) err = KDTN_E_REMOTE_CIDR;
 
-    RpVals pv;
-#pragma unroll
-    for (int k = 0; k < KDTN_NPROP; ++k) pv.v[k] = 0;
-    pv.lat_t = pv.jit_t = pv.rate_hi = pv.bad = 0;
-    uint32_t any = M.gap;
-#pragma unroll
-    for (int k = 0; k < KDTN_NPROP; ++k) any |= M.pl[k];
-    if (any) {
-#pragma unroll 1
-        for (uint32_t k = 0; k < (uint32_t)KDTN_NPROP; ++k) {      // three call sites, not twelve
-            uint32_t off = 0, len = 0;
-#pragma unroll
-            for (int j = 0; j < KDTN_NPROP; ++j) {
-                off = k == (uint32_t)j ? M.po[j] : off;
-                len = k == (uint32_t)j ? M.pl[j] : len;
-            }
-            if (!len) continue;
-            const uint8_t* s = at(off);
-            uint32_t x = 0, y = 0;
-            bool ok;
-            if (k == KDTN_P_LATENCY || k == KDTN_P_JITTER) {
-                ok = parse_duration_us(s, len, &x);
-                y = time2tick(x, in.tick);
-            } else if (k == KDTN_P_RATE) {
-                uint64_t r = 0;
-                ok = parse_rate(s, len, &r);
-                x = (uint32_t)r;
-                y = (uint32_t)(r >> 32);
-            } else {
-                float pct = 0.f;
-                ok = parse_pct(s, len, &pct);
-                x = ok ? p2u(pct) : 0u;
-            }
-            if (!ok) {
-                x = y = 0;
-                pv.bad |= 1u << k;
-            }
-#pragma unroll
-            for (int j = 0; j < KDTN_NPROP; ++j) pv.v[j] = k == (uint32_t)j ? x : pv.v[j];
-            pv.lat_t = k == KDTN_P_LATENCY ? y : pv.lat_t;
-            pv.jit_t = k == KDTN_P_JITTER ? y : pv.jit_t;
-            pv.rate_hi = k == KDTN_P_RATE ? y : pv.rate_hi;
-        }
-    }
-    qdisc_from_parsed(pv, M.gap, any == 0, Q);
-    if (!err) err = (Q[17] >> 16) & 0xFFu;
+    const uint32_t qerr = qdisc_plan(at, M.po, M.pl, M.gap, in.tick, Q);
+    if (!err) err = qerr;
 
     // handler.go:177-185: Get(vni) found and the stored netns is not this message's
     const uint32_t ent = rp_lookup(in, M.vni);
@@ -293,7 +189,7 @@ __global__ void __launch_bounds__(UW_BLOCK) k_rp_plan(RpIn in, uint4* plan, uint
                 uint32_t hi = on && lane >= cur && lane < cur + run ? e : base;
 #pragma unroll
                 for (int o = 32; o >= 1; o >>= 1) hi = max(hi, (uint32_t)__shfl_xor(hi, o, 64));
-                rp_fill(win, in, w, base, (hi - base + 15u) & ~15u);
+                uw_fill_span(win, in.doc, w, base, (hi - base + 15u) & ~15u);
             } else {
                 run = 1;                                    // larger than the window: from memory
             }

@@ -207,6 +207,29 @@ REMOTE_PLAN_DTYPE = np.dtype([("str", np.dtype([("off", np.uint32), ("len", np.u
 assert REMOTE_PLAN_DTYPE.itemsize == 64
 
 
+class UpdateIn(C.Structure):
+    _fields_ = [("n_msgs", C.c_uint32), ("off", C.c_void_p)]
+
+
+class UpdateOut(C.Structure):
+    _fields_ = [("msg", C.c_void_p), ("link", C.c_void_p), ("qdisc", C.c_void_p), ("link_cap", C.c_uint32),
+                ("n_links", C.c_uint32)]
+
+
+class UpdateIngestPlan(C.Structure):
+    """kdtn_update_ingest_plan_t: what the last kdtn_update_ingest did."""
+    _fields_ = [(f, C.c_uint32) for f in ("window_bytes", "n_long", "n_direct", "n_rejected", "n_links", "n_cut")]
+
+
+_STR = np.dtype([("off", np.uint32), ("len", np.uint32)])
+UPDATE_MSG_DTYPE = np.dtype([("net_ns", _STR), ("name", _STR), ("link_base", np.uint32), ("n_links", np.uint32),
+                             ("cut", np.uint32), ("wire_err", np.uint8), ("err", np.uint8), ("reserved", np.uint16)])
+UPDATE_LINK_DTYPE = np.dtype([("local_intf", _STR), ("uid", np.int64), ("msg", np.uint32), ("index", np.uint32),
+                              ("err", np.uint8), ("has_props", np.uint8), ("reserved0", np.uint16),
+                              ("reserved", np.uint32)])
+assert UPDATE_MSG_DTYPE.itemsize == 32 and UPDATE_LINK_DTYPE.itemsize == 32
+
+
 class IngestInfo(C.Structure):
     _fields_ = [("n_topos", C.c_uint32), ("n_desired", C.c_uint32), ("n_realised", C.c_uint32),
                 ("n_kdict", C.c_uint32), ("n_pdict", C.c_uint32), ("json_err", C.c_int32),
@@ -257,7 +280,8 @@ EXPORTS = ["kdtn_version", "kdtn_strerror", "kdtn_err_name", "kdtn_init", "kdtn_
            "kdtn_vni_ops_export", "kdtn_vni_ops_import", "kdtn_json_ingest_delta",
            "kdtn_epoch_download_async", "kdtn_epoch_download_wait", "kdtn_epoch_late_pods",
            "kdtn_epoch_plan", "kdtn_epoch_status_encode", "kdtn_epoch_download_status",
-           "kdtn_wire_ingest", "kdtn_wire_ingest_plan", "kdtn_remote_ingest", "kdtn_remote_ingest_plan"]
+           "kdtn_wire_ingest", "kdtn_wire_ingest_plan", "kdtn_remote_ingest", "kdtn_remote_ingest_plan",
+           "kdtn_update_ingest", "kdtn_update_ingest_plan"]
 
 
 def ptr(a: np.ndarray, t):

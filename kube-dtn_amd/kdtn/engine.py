@@ -123,6 +123,8 @@ def lib() -> C.CDLL:
         "kdtn_wire_ingest_plan": (C.c_int, [vp, C.POINTER(abi.WirePlan)]),
         "kdtn_remote_ingest": (C.c_int, [vp, C.POINTER(abi.RemoteIn), vp, vp]),
         "kdtn_remote_ingest_plan": (C.c_int, [vp, C.POINTER(abi.RemoteIngestPlan)]),
+        "kdtn_update_ingest": (C.c_int, [vp, C.POINTER(abi.UpdateIn), C.POINTER(abi.UpdateOut)]),
+        "kdtn_update_ingest_plan": (C.c_int, [vp, C.POINTER(abi.UpdateIngestPlan)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -444,6 +446,33 @@ class Engine:
         """What the last remote_ingest did (kdtn_remote_ingest_plan)."""
         p = abi.RemoteIngestPlan()
         _check(lib().kdtn_remote_ingest_plan(self._ctx, C.byref(p)), "kdtn_remote_ingest_plan")
+        return p
+
+    def update_ingest(self, stream: bytes, off):
+        """kdtn_update_ingest: Local.UpdateLinks request bodies (message m = stream[off[m],
+        off[m+1])) decoded and planned on the GPU. Returns (msgs, links, qdiscs):
+        abi.UPDATE_MSG_DTYPE per message, abi.UPDATE_LINK_DTYPE and abi.QDISC_DTYPE per link."""
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        if len(off) < 1:
+            raise ValueError("off must hold one more entry than there are messages")
+        self.json_upload(bytes(stream))
+        n = len(off) - 1
+        msgs = np.zeros(max(n, 1), abi.UPDATE_MSG_DTYPE)
+        uin = abi.UpdateIn(n, off.ctypes.data if n else None)
+        cap = len(stream) // 64 + 64                   # an ordinary link takes more bytes than that
+        for fetch in (False, True):                    # the records stay on the device for a second, larger fetch
+            links, qdiscs = np.zeros(cap, abi.UPDATE_LINK_DTYPE), np.zeros(cap, abi.QDISC_DTYPE)
+            out = abi.UpdateOut(msgs.ctypes.data, links.ctypes.data, qdiscs.ctypes.data, cap, 0)
+            _check(lib().kdtn_update_ingest(self._ctx, None if fetch else C.byref(uin), C.byref(out)), "kdtn_update_ingest")
+            if out.n_links <= cap:
+                break
+            cap = out.n_links
+        return msgs[:n], links[:out.n_links], qdiscs[:out.n_links]
+
+    def update_plan(self) -> abi.UpdateIngestPlan:
+        """What the last update_ingest did (kdtn_update_ingest_plan)."""
+        p = abi.UpdateIngestPlan()
+        _check(lib().kdtn_update_ingest_plan(self._ctx, C.byref(p)), "kdtn_update_ingest_plan")
         return p
 
     def ingest_doc_index(self) -> np.ndarray:
